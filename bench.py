@@ -2,7 +2,7 @@
 """Headline benchmark: RefreshMessage::collect() proofs verified per second at
 n = 64 (60 refresh + 4 JoinMessage replacements, t = 32, 2048-bit Paillier N,
 M = 256) — BASELINE.json configs[2], the configuration the metric is quoted
-on; plus the metric's second half, 4096-bit modexp/s/GPU (exponent N,
+on; plus, with --full, the metric's second half, 4096-bit modexp/s/GPU (exponent N,
 modulus N^2), and BASELINE configs[4] (many independent t=1 n=3 sessions with
 3072-bit keys in one device pass) as an extra object on the same line.
 
@@ -15,7 +15,14 @@ paillier_key_vec updates and the share recovery (GPU decryption + pk_vec MSM,
 overlapped with the pipeline), on a fresh copy of the LocalKey each step.
 With --gpus N (torchrun) each rank verifies a slice of the messages and the
 verdict bytes are all-reduced over RCCL (fsdkr.shard.collect).  Inputs are
-synthetic, generated on the GPU with a seeded prover (fsdkr.synth)."""
+synthetic, generated on the GPU with a seeded prover (fsdkr.synth).
+
+A plain run generates the workload, warms up, times --steps steps and prints
+the headline line (value, ms_per_step, the step's MAC accounting).  --full adds
+every other leg to that line, each a run of its own after the timed steps: the
+phases of a call, metric 2 and its roofline, configs[3], configs[4], key
+generation and the CPU baseline.  --dump-outputs DIR writes the LocalKey the
+last timed step produced as DIR/<name>.npy."""
 import argparse
 import copy
 import json
@@ -489,6 +496,35 @@ def config3_bench(ctx, steps, seed, n=256, t=128, dist=None, dev=None):
             "data": f"synthetic (seeded GPU prover fs-dkr_amd/fsdkr/synth.py); {n} distinct refresh messages"}
 
 
+def _limbs(values, bits):
+    """Integers as little-endian 32-bit limbs in float64 (exact), one row each."""
+    k = (bits + 31) // 32
+    out = np.zeros((len(values), k), dtype=np.float64)
+    for r, v in enumerate(values):
+        assert 0 <= v < 1 << (32 * k), "output wider than its limb row"
+        out[r] = np.frombuffer(v.to_bytes(4 * k, "little"), dtype="<u4")
+    return out
+
+
+def _point_limbs(points):
+    """Affine secp256k1 points as rows of x | y limbs; the point at infinity is all zero."""
+    return np.hstack([_limbs([p[0] if p else 0 for p in points], 256), _limbs([p[1] if p else 0 for p in points], 256)])
+
+
+def dump_outputs(path, key, key_bits):
+    """What a caller of collect() receives from the last timed step: the LocalKey
+    it updated (new share x_i, public key y, pk_vec, every party's Paillier N),
+    each integer as 32-bit limbs held exactly in float64.  collect() returned
+    None (every proof accepted) or the benchmark would have stopped."""
+    os.makedirs(path, exist_ok=True)
+    nbits = max([key_bits] + [ek.n.bit_length() for ek in key.paillier_key_vec])
+    arrays = {"x_i": _limbs([key.x_i], 256), "y": _point_limbs([key.y]), "pk_vec": _point_limbs(key.pk_vec),
+              "paillier_key_vec_n": _limbs([ek.n for ek in key.paillier_key_vec], nbits)}
+    assert sum(v.nbytes for v in arrays.values()) <= 64 << 20
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -512,6 +548,11 @@ def main():
                     help="analysis only: run rank 0's slice of a W-way shard on one GPU and report its step time")
     ap.add_argument("--gap-ms", type=float, default=0.0,
                     help="with --emulate-shard: idle gap before each timed whole-call step (profiling)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (phases, metric 2 and its roofline, "
+                         "configs[3], configs[4], key generation, the CPU baseline) and add them to the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed collect() left in its LocalKey as DIR/<name>.npy (float64)")
     a = ap.parse_args()
 
     import torch
@@ -630,11 +671,42 @@ def main():
     ms_per_step = elapsed / a.steps * 1e3
     proofs = proofs_of(R, J, n)
     value = proofs * a.steps / elapsed
+    if a.dump_outputs and rank == 0 and a.steps:
+        dump_outputs(a.dump_outputs, keys[a.warmup + a.steps - 1], a.key_bits)
+    out = {
+        "metric": METRIC, "value": value, "unit": "proofs/s", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "u32 (radix-2^29 digits, u64 accumulators)",
+        "data": "synthetic (seeded GPU prover fs-dkr_amd/fsdkr/synth.py; 2048-bit Paillier/DLog keys)" +
+                (f"; {a.unique_msgs} distinct refresh messages tiled to {R}" if a.unique_msgs and a.unique_msgs < R
+                 else ""),
+        "config": {"workload": f"RefreshMessage::collect n={n} t={t}: {R} refresh + {J} JoinMessage, M=256, "
+                               f"{a.key_bits}-bit N (BASELINE configs[{3 if n >= 256 else 2}]); one step = the whole "
+                               f"collect() call (pack, pre-pass + upload, pipeline, first error, key updates, "
+                               f"share recovery)",
+                   "n": n, "t": t, "refresh": R, "joins": J,
+                   "proofs_per_step": proofs, "parallelism": f"refresh messages sharded over {world} GPU(s)"},
+        "collect_efficiency": efficiency(collect_work(R, J, n), collect_issued(R, J, n), ms_per_step * 1e-3, world,
+                                         pmc=pmc_per_call("n64") if (n, J) == (64, 4) else None),
+        "workload_gen_s": gen_s,
+    }
+    if a.full:
+        full_legs(a, out, ctx, dist, dev, rank, world, msgs, joins, lk, proofs)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def full_legs(a, out, ctx, dist, dev, rank, world, msgs, joins, lk, proofs):
+    """--full: the legs beside the headline, each a run of its own, added to the
+    result line `out`: configs[3] (every rank), then on rank 0 the phases of a
+    call, metric 2 with its roofline, the CPU baseline, configs[4] and key
+    generation."""
+    n = a.n
     # configs[3] (n = 256): on one GPU, or sharded over every rank of the group
     c3 = config3_bench(ctx, a.config3_steps, a.seed + 3, dist=dist, dev=dev) if a.config3_steps and n != 256 else None
     if rank != 0:
-        if dist is not None:
-            dist.destroy_process_group()
         return
     ctx.set_cu_split(0)   # a shard slice may have split the CUs; the single-GPU figures below use the whole chip
     batch, verd, ph = phases(ctx, msgs, lk, joins, a.key_bits)
@@ -649,21 +721,8 @@ def main():
             cpu["cpp_unavailable"] = str(e)
     s4 = sessions_bench(ctx, a.sessions, a.session_steps, a.seed + 4) if a.sessions and world == 1 else None
     kg = keygen_bench(ctx) if world == 1 else None
-    W_collect = collect_work(R, J, n)
     traffic, traffic_src, l2_hit = pmc_traffic(roof["count"])
-    out = {
-        "metric": METRIC, "value": value, "unit": "proofs/s", "n_gpus": world, "steps": a.steps,
-        "warmup": a.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "u32 (radix-2^29 digits, u64 accumulators)",
-        "data": "synthetic (seeded GPU prover fs-dkr_amd/fsdkr/synth.py; 2048-bit Paillier/DLog keys)" +
-                (f"; {a.unique_msgs} distinct refresh messages tiled to {R}" if a.unique_msgs and a.unique_msgs < R
-                 else ""),
-        "config": {"workload": f"RefreshMessage::collect n={n} t={t}: {R} refresh + {J} JoinMessage, M=256, "
-                               f"{a.key_bits}-bit N (BASELINE configs[{3 if n >= 256 else 2}]); one step = the whole "
-                               f"collect() call (pack, pre-pass + upload, pipeline, first error, key updates, "
-                               f"share recovery)",
-                   "n": n, "t": t, "refresh": R, "joins": J,
-                   "proofs_per_step": proofs, "parallelism": f"refresh messages sharded over {world} GPU(s)"},
+    out.update({
         "phases_ms": ph,
         "device_pipeline_proofs_per_s": proofs / (ph["device_pipeline_ms"] * 1e-3),
         "modexp_4096_per_s": roof["modexp_per_s"],
@@ -687,17 +746,11 @@ def main():
                                    "int-MAC peak it actually uses",
                      "issued": roof["issued_mac_per_s"] / 1e12, "issued_frac": roof["issued_mac_per_s"] / PEAK_MAC,
                      "lanes_per_instance": roof["group"]},
-        "collect_efficiency": efficiency(W_collect, collect_issued(R, J, n), ms_per_step * 1e-3, world,
-                                         pmc=pmc_per_call("n64") if (n, J) == (64, 4) else None),
         "config3": c3,
         "config4_sessions": s4,
         "keygen": kg,
-        "workload_gen_s": gen_s,
         "cpu_baseline": cpu,
-    }
-    print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
+    })
 
 
 if __name__ == "__main__":

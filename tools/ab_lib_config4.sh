@@ -8,7 +8,7 @@ O=gpurun_out/$TAG; mkdir -p $O
 for r in $(seq $ROUNDS); do
   for v in A B; do
     if [ $v = A ]; then export FSDKR_LIB=$A; else export FSDKR_LIB=$B; fi
-    timeout -k 10 300 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --config3-steps 0 --session-steps 3 \
+    timeout -k 10 300 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --config3-steps 0 --session-steps 3 \
       >> $O/bench_$v.jsonl 2>> $O/bench_$v.err || exit 1
     echo "round $r $v done"
   done

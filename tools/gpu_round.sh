@@ -6,10 +6,10 @@
 #   tests            the whole -m gpu suite                      -> tests.log
 #   tests:F1,F2      those test files only (tests/F1, tests/F2)  -> tests.log
 #   smoke            __graft_entry__ build-free smoke             -> smoke.log
-#   bench            bench.py (default: n = 64 headline, metric 2, configs[3] n = 256,
+#   bench            bench.py --full ( n = 64 headline, metric 2, configs[3] n = 256,
 #                    configs[4], key generation, CPU baseline)    -> bench.json
-#   benchq           bench.py without the CPU baseline            -> bench.json
-#   prof             rocprofv3 --kernel-trace --stats of a short bench.py run -> prof/
+#   benchq           bench.py --full without the CPU baseline            -> bench.json
+#   prof             rocprofv3 --kernel-trace --stats of a short bench.py --full run -> prof/
 #   trace            kernel trace of whole n = 64 collect() calls + timeline of one -> trace_summary.txt
 #   trace4           the same for whole configs[4] collect_many() calls (1024 sessions) -> trace4_summary.txt
 #   trace256         the same for whole n = 256 collect() calls (configs[3])  -> trace256_summary.txt
@@ -65,11 +65,11 @@ for step in "$@"; do
                > $OUT/tests.log 2>&1 || fail tests $? $OUT/tests.log ;;
     smoke) timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 \
              || fail smoke $? $OUT/smoke.log ;;
-    bench) timeout -k 10 600 python $R/bench.py > $OUT/bench.json 2> $OUT/bench.err || fail bench $? $OUT/bench.err ;;
-    benchq) timeout -k 10 500 python $R/bench.py --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err \
+    bench) timeout -k 10 600 python $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err || fail bench $? $OUT/bench.err ;;
+    benchq) timeout -k 10 500 python $R/bench.py --full --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err \
               || fail bench $? $OUT/bench.err ;;
     prof) (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench \
-             -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/prof.log 2>&1) \
+             -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/prof.log 2>&1) \
              || fail prof $? $OUT/prof.log ;;
     trace) (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o tr \
               -- python3 $R/tools/prof_collect.py --full --steps 4 > $OUT/trace.log 2>&1) || fail trace $? $OUT/trace.log
@@ -111,11 +111,11 @@ for step in "$@"; do
       done ;;
     rehearse2)   # bench.py --gpus 2 as the driver launches it, both ranks on GPU 0 over gloo
       FSDKR_BENCH_REHEARSE=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29517 $R/bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline \
+        --master-addr 127.0.0.1 --master-port 29517 $R/bench.py --gpus 2 --full --steps 3 --warmup 1 --no-cpu-baseline \
         --sessions 0 --config3-steps 1 > $OUT/rehearse2.json 2> $OUT/rehearse2.err || fail rehearse2 $? $OUT/rehearse2.err ;;
     rehearse4)   # the same with four ranks (shard_range over 4, max over 4 ranks)
       FSDKR_BENCH_REHEARSE=1 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 \
-        --master-addr 127.0.0.1 --master-port 29519 $R/bench.py --gpus 4 --steps 3 --warmup 1 --no-cpu-baseline \
+        --master-addr 127.0.0.1 --master-port 29519 $R/bench.py --gpus 4 --full --steps 3 --warmup 1 --no-cpu-baseline \
         --sessions 0 --config3-steps 1 > $OUT/rehearse4.json 2> $OUT/rehearse4.err || fail rehearse4 $? $OUT/rehearse4.err ;;
     *) timeout -k 10 600 bash -c "$step" > $OUT/extra.log 2>&1 || fail "$step" $? $OUT/extra.log ;;
   esac

@@ -9,5 +9,5 @@ FSDKR_LIB=$R/abtmp/PF.so timeout -k 10 900 python -u -m pytest $R/tests/test_fix
   $R/tests/test_configs_gpu.py $R/tests/test_timed_path_gpu.py -m gpu -x -q --timeout 400 --timeout-method thread > $O/tests.log 2>&1 \
   || { echo tests failed; tail -30 $O/tests.log; exit 1; }
 tail -2 $O/tests.log
-bash tools/ab_libs.sh r06zd_pf/ab 3 "python bench.py --steps 10 --warmup 2 --no-cpu-baseline --config3-steps 0" \
+bash tools/ab_libs.sh r06zd_pf/ab 3 "python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --config3-steps 0" \
   abtmp/A.so abtmp/PF.so || exit 1

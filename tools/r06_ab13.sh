@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r06ze_pf; mkdir -p $O
 bash tools/ab_libs.sh r06ze_pf/n64 5 "python bench.py --steps 12 --warmup 2 --no-cpu-baseline --sessions 0 --config3-steps 0" \
   abtmp/A.so abtmp/PF.so || exit 1
-bash tools/ab_libs.sh r06ze_pf/c4 3 "python bench.py --steps 2 --warmup 1 --no-cpu-baseline --config3-steps 0 --session-steps 3 --modexp-count 4096" \
+bash tools/ab_libs.sh r06ze_pf/c4 3 "python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --config3-steps 0 --session-steps 3 --modexp-count 4096" \
   abtmp/A.so abtmp/PF.so || exit 1
 (cd /tmp && FSDKR_LIB=$R/abtmp/PF.so timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace -o tr \
    -- python3 $R/tools/prof_collect.py --full --steps 4 > $O/trace.log 2>&1) || { echo trace failed; exit 1; }

@@ -9,5 +9,5 @@ FSDKR_LIB=$R/abtmp/GBE.so timeout -k 10 900 python -u -m pytest $R/tests/test_co
   $R/tests/test_modexp_gpu.py $R/tests/test_golden_gpu.py $R/tests/test_distribute_gpu.py $R/tests/test_configs_gpu.py \
   -m gpu -x -v --timeout 400 --timeout-method thread > $O/tests.log 2>&1 || { echo tests failed; tail -30 $O/tests.log; exit 1; }
 tail -2 $O/tests.log
-bash tools/ab_libs.sh r06v_gbe/ab 3 "python bench.py --steps 10 --warmup 2 --no-cpu-baseline --sessions 0 --config3-steps 2" \
+bash tools/ab_libs.sh r06v_gbe/ab 3 "python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --sessions 0 --config3-steps 2" \
   abtmp/HEAD.so abtmp/GBE.so || exit 1
