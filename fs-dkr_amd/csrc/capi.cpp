@@ -341,7 +341,8 @@ int launch_modexp_desc(Ctx* c, uint32_t k32, uint32_t count, uint32_t exp_bits, 
     return FSDKR_E_UNSUPPORTED;
   }
   const uint32_t ebits = exp_bits ? exp_bits : 1;
-  const uint32_t w = slide ? choose_slide_window(ebits) : choose_window(ebits);
+  const bool nadic = split && split->lo_bit && split->nadic;   // its head and tail run 7-bit windows
+  const uint32_t w = nadic ? kNadicWindow : slide ? choose_slide_window(ebits) : choose_window(ebits);
   const uint32_t nwin = (ebits + w - 1) / w;
   const size_t entries = slide ? ((size_t)1 << (w - 1)) + 1 : (size_t)1 << w;
   uint32_t* d_table = (uint32_t*)c->buf(table_tag, sizeof(uint32_t) * (size_t)count * entries * KD);
@@ -374,6 +375,11 @@ int launch_modexp_desc(Ctx* c, uint32_t k32, uint32_t count, uint32_t exp_bits, 
       return FSDKR_E_ARG;
     }
     const std::string base(table_tag);
+    if (nadic && grp != 16) {
+      c->fail("the N-adic head needs the 16-lane shape (group %u)", grp);
+      return FSDKR_E_ARG;
+    }
+    a.nadic = split->nadic;
     a.lo_bit = split->lo_bit;
     a.tail = split->tail ? 1u : 0u;
     a.state = (uint32_t*)c->buf((base + "_state").c_str(), (size_t)count * KD * 4);

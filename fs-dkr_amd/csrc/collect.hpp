@@ -344,7 +344,12 @@ struct CollectPlan {
     const uint32_t* cons = nullptr;
     uint32_t* out = nullptr;
     uint32_t count = 0, bits = 0, group = 0, flags = 0;
+    const uint32_t* nadic = nullptr;   // the head ran N-adic with these constants (GaPre::nadic)
   } ga_tail;
+  // prepare's own GA (no prestart hit) runs the N-adic head: its constants per receiver
+  // (nadic_consts) lie in the image at o_nadic
+  bool nadic_own = false;
+  size_t o_nadic = 0;
   std::vector<uint8_t> ae_zero;        // Alice e == 0: c^0 = 1 whatever c is
   // device words finish reads back (the plan's output region)
   const void *r_unn = nullptr, *r_uzA = nullptr, *r_uzp = nullptr, *r_pdlv = nullptr, *r_fel = nullptr;
@@ -376,6 +381,9 @@ struct GaPre {
   // split GA (ga_split_ok): the prestart ran the HEAD; prepare launches the joint tail
   // with these descriptors (ga_rows: out_idx of every instance, pads = 2P)
   bool split = false;
+  // the head ran in half-width N-adic form (ga_nadic_ok) with these device constants
+  // (nullptr: the full-width head); the tail must be launched with the same setting
+  const uint32_t* nadic = nullptr;    // (in the prestart's device image, beside the moduli)
   uint32_t ga_group = 0, ga_flags = 0, ga_count = 0, ga_bits = 0;
   const uint8_t* ga_desc = nullptr;
   std::vector<uint32_t> ga_rows;
@@ -513,6 +521,14 @@ inline uint32_t ga_prio() { return 2u; }
 inline bool ga_split_ok(uint32_t nn, uint32_t group, uint32_t flags) {
   return nn == 128 && (flags & kDescSlide) && (flags & kDescOutIdx) &&
          (group == 4 || group == 8 || group == 16 || group == kWideGroup);
+}
+// GA's head in half-width N-adic Montgomery form (modexp.hip modexp_nadic_head_kernel):
+// the split 16-lane shape of 2048-bit receivers (N^2 of 128 limbs, bases s2 / s and
+// N at 64 limbs), every N odd (the caller's check).  FSDKR_CFG_GA_FULLWIDTH keeps
+// the full-width head (parity tests, A/B); results are identical.
+inline bool ga_nadic_ok(const Ctx* c, uint32_t nn, uint32_t nl, uint32_t group, uint32_t flags) {
+  return !(c->flags & FSDKR_CFG_GA_FULLWIDTH) && nn == 128 && nl == 64 && group == 16 && ga_split_ok(nn, group, flags) &&
+         !c->ct && (c->modexp_group == 0 || c->modexp_group == 16);
 }
 // the tail's per-instance descriptor block: base2_ptr u64 | exp2_ptr u64 | exp2_len u32
 constexpr size_t kTailDescBytes = 20;

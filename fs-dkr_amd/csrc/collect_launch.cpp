@@ -141,12 +141,15 @@ int collect_launch_impl(Ctx* c) {
       tail.d_desc2 = dev + pl.d_desc2;
       if (pl.ga_hit) {   // the prestarted head runs on this stream: its tail follows c^-1
         const CollectPlan::GaTail& t = pl.ga_tail;
+        tail.nadic = t.nadic;   // as the head ran
         (void)hipStreamWaitEvent(ss, inv_done, 0);
         if ((rc = launch_modexp_desc(c, nn, t.count, t.bits, t.desc, t.cons, t.out, ss, "mxt_GApre", ga_prio(), t.group,
                                      t.flags, &tail)) ||
             (rc = c->hip_check(hipEventRecord(pl.ga_done, ss), "event record")))   // the s^N rows: after the tail
           return rc;
       } else if (pl.jcount[0]) {
+        // the N-adic head, from prepare's constants in the image
+        if (pl.nadic_own && ga_nadic_ok(c, nn, nl, ga_group, pl.jflags[0])) head.nadic = tail.nadic = PI(pl.o_nadic);
         if ((rc = launch_modexp_desc(c, nn, pl.jcount[0], pl.jbits[0], dev + pl.d_J[0], cga, PX(pl.x_J[0]), ss, "mxt_GA",
                                      prio[0], ga_group, pl.jflags[0], &head)))
           return rc;

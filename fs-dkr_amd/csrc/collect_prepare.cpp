@@ -121,15 +121,27 @@ int collect_prepare_impl(Ctx* c, const fsdkr_collect_batch* bs, uint32_t count) 
   }
   if (pl.joint && pl.ga_hit)
     pl.ga_tail = CollectPlan::GaTail{gpre->ga_desc, gpre->cons, gpre->out, gpre->ga_count, gpre->ga_bits, gpre->ga_group,
-                                     gpre->ga_flags};
+                                     gpre->ga_flags, gpre->nadic};
+  // prepare's own GA: the N-adic head where its shape holds and every N is odd
+  bool nadic_own = false;
+  if (pl.joint && !pl.ga_hit) {
+    const uint32_t g0 = ga_lanes(2 * P, nn);
+    nadic_own = ga_nadic_ok(c, nn, nl, g0, ga_desc_flags(true, g0));
+    for (uint32_t r = 0; r < n && nadic_own; ++r) {
+      const Sess& x = pl.ss[sess_of_recv[r]];
+      nadic_own = (x.b->recv_n[(size_t)(r - x.rbase) * x.b->nl] & 1u) != 0;
+    }
+  }
+  std::vector<uint32_t> nadic_host(nadic_own ? (size_t)n * kNadicStride : 0, 0u);
   clk.lap("shapes");
 
   // ---------------- host pre-pass (O(n) + O(P) scans, no big exponentiations; threaded)
   std::vector<uint32_t> NN((size_t)n * nn), NP1((size_t)n * nn), recv_bits(n);
-  parallel_for(n, 64, [&](size_t b0, size_t b1) {
+  parallel_for(n, nadic_own ? 1 : 64, [&](size_t b0, size_t b1) {
     for (size_t r = b0; r < b1; ++r) {
       const Sess& x = pl.ss[sess_of_recv[r]];
       const uint32_t* Np = x.b->recv_n + (size_t)(r - x.rbase) * x.b->nl;
+      if (nadic_own) nadic_consts(Np, x.b->nl, nadic_host.data() + r * kNadicStride);
       hbn::Limbs N = hbn::from(Np, x.b->nl);
       hbn::store(hbn::mul(N, N), NN.data() + r * nn, nn);
       hbn::store(hbn::add_small(N, 1), NP1.data() + r * nn, nn);
@@ -468,6 +480,8 @@ int collect_prepare_impl(Ctx* c, const fsdkr_collect_batch* bs, uint32_t count) 
   const size_t o_rn = field(&B::recv_n, R_recv, W_nl, nl), o_rt = field(&B::recv_ntilde, R_recv, W_nl, nl);
   const size_t o_h1 = field(&B::recv_h1, R_recv, W_nl, nl), o_h2 = field(&B::recv_h2, R_recv, W_nl, nl);
   const size_t o_NN = I.own(NN), o_NP1 = I.own(NP1);
+  pl.nadic_own = nadic_own;
+  pl.o_nadic = nadic_own ? I.own(nadic_host) : 0;
   const size_t o_enc = field(&B::enc, R_pair, W_nn, nn), o_Q = field(&B::commit, R_pair, W_16, 16);
   const size_t o_pz = field(&B::pdl_z, R_pair, W_nl, nl), o_pu1 = field(&B::pdl_u1, R_pair, W_16, 16);
   const size_t o_pu2 = field(&B::pdl_u2, R_pair, W_nn, nn), o_pu3 = field(&B::pdl_u3, R_pair, W_nl, nl);

@@ -7,6 +7,42 @@
 
 namespace fsdkr {
 
+// The per-modulus constants of GA's half-width N-adic head (modexp.hip
+// modexp_nadic_head_kernel, layout in kernels.h), all from N alone:
+//   N' = N k0, k0 = -N^-1 mod 2^29        the quotient-scaled modulus of the 72-digit rows
+//   (r, (N' - q) mod N')                  M(R): (q, r) = divmod(R^2 mod N'^2, N'), so that
+//                                         r - ((N' - q) mod N') N' = R^2 (mod N'^2)
+//   C1 = R^3 mod N^2, C2 = -N' C1 mod N^2 the tail's hand-over: x0 C1 + x1 C2 = X R^3
+// with R = 2^(29*72).
+void nadic_consts(const uint32_t* N, uint32_t nl, uint32_t* out) {
+  constexpr uint32_t kM29 = (1u << 29) - 1;
+  auto digits = [&](const hbn::Limbs& v, uint32_t* dst, int nd) {
+    for (int j = 0; j < nd; ++j) {
+      const size_t bit = 29u * (size_t)j, w = bit >> 5, sh = bit & 31;
+      const uint64_t lo = w < v.size() ? v[w] : 0u, hi = w + 1 < v.size() ? v[w + 1] : 0u;
+      dst[j] = (uint32_t)(((hi << 32) | lo) >> sh) & kM29;
+    }
+  };
+  std::fill(out, out + kNadicStride, 0u);
+  const hbn::Limbs n = hbn::from(N, nl);
+  uint32_t inv = N[0];
+  for (int it = 0; it < 5; ++it) inv *= 2u - N[0] * inv;
+  const uint32_t k0 = (0u - inv) & kM29;
+  const hbn::Limbs Np = hbn::mul(n, hbn::Limbs{k0});
+  const hbn::Limbs one{1u};
+  hbn::Limbs q, r;
+  hbn::divmod_knuth(hbn::mod(hbn::shl(one, 2 * 29 * 72), hbn::mul(Np, Np)), Np, &q, &r);
+  const hbn::Limbs nq = q.empty() ? hbn::Limbs{} : hbn::sub(Np, q);
+  const hbn::Limbs NN = hbn::mul(n, n);
+  const hbn::Limbs C1 = hbn::mod(hbn::shl(one, 3 * 29 * 72), NN);
+  const hbn::Limbs C2 = hbn::mod(hbn::mul(hbn::sub(NN, hbn::mod(Np, NN)), C1), NN);
+  digits(Np, out + kNadicNp, 72);
+  digits(r, out + kNadicR0, 72);
+  digits(nq, out + kNadicR1, 72);
+  digits(C1, out + kNadicC1, 144);
+  digits(C2, out + kNadicC2, 144);
+}
+
 
 // The fixed-base table chains of collect()'s FbJob, in its base order: h1_i, h2_i
 // of every receiver's DLogStatement (h2: one squaring per exponent bit of s3,
@@ -352,13 +388,17 @@ int prestart_ga(Ctx* c, const fsdkr_collect_batch* bs, uint32_t count, uint32_t*
     P += R * ns;
   }
   const uint32_t nn = 2 * nl;
-  // image: [N^2 | N | s2 | s | descriptors], outputs after it
-  auto al = Img::al;
-  const size_t o_NN = 0, o_rn = al((size_t)n * nn * 4), o_s2 = o_rn + al((size_t)n * nl * 4),
-               o_s = o_s2 + al((size_t)P * nl * 4), o_desc = o_s + al((size_t)P * nl * 4);
   // the lanes launch() would give GA: 32 lanes (KD = 160 constants) for the small
   // batches of a multi-GPU shard, where GA's chain latency is the critical path
   const uint32_t group = ga_lanes(2 * P, nn), per_wave = ga_per_wave(group, nn);
+  // the N-adic head's constants, beside N^2 (every N is odd here); used if the
+  // regrouped job keeps its sliding-window shape (below)
+  const bool nadic_early = ga_nadic_ok(c, nn, nl, group, ga_desc_flags(true, group));
+  // image: [N^2 | N | N-adic constants | s2 | s | descriptors], outputs after it
+  auto al = Img::al;
+  const size_t o_NN = 0, o_rn = al((size_t)n * nn * 4), o_nad = o_rn + al((size_t)n * nl * 4),
+               o_s2 = o_nad + (nadic_early ? al((size_t)n * kNadicStride * 4) : 0),
+               o_s = o_s2 + al((size_t)P * nl * 4), o_desc = o_s + al((size_t)P * nl * 4);
   // descriptors with out_idx, for 2P chains + at most per_wave - 1 pads per receiver
   const size_t desc_bytes = ((size_t)2 * P + (size_t)n * (per_wave ? per_wave - 1 : 0)) * 36,
                o_out = o_desc + al(desc_bytes);
@@ -387,8 +427,10 @@ int prestart_ga(Ctx* c, const fsdkr_collect_batch* bs, uint32_t count, uint32_t*
   uint32_t* S1 = reinterpret_cast<uint32_t*>(img + o_s);
   std::vector<uint32_t> rbits(n);
   std::vector<uint32_t> sess_of_recv(n);
+  g.nadic = nullptr;
+  uint32_t* NAD = reinterpret_cast<uint32_t*>(img + o_nad);
   for (uint32_t k = 0; k < count; ++k) std::fill(sess_of_recv.begin() + ss[k].rbase, sess_of_recv.begin() + ss[k].rbase + ss[k].n, k);
-  parallel_for(n, 4, [&](size_t r0, size_t r1) {   // N^2 per receiver: 64 products of 2048-bit N at n = 64, ~5 us each
+  parallel_for(n, nadic_early ? 1 : 4, [&](size_t r0, size_t r1) {   // N^2 per receiver: 64 products of 2048-bit N at n = 64, ~5 us each
     for (size_t r = r0; r < r1; ++r) {
       const GaPre::Sess& x = ss[sess_of_recv[r]];
       const uint32_t* Np = bs[sess_of_recv[r]].recv_n + (r - x.rbase) * x.nl;
@@ -396,6 +438,7 @@ int prestart_ga(Ctx* c, const fsdkr_collect_batch* bs, uint32_t count, uint32_t*
       hbn::store(hbn::mul(N, N), NN + r * nn, nn);
       memcpy(RN + r * nl, Np, (size_t)x.nl * 4);
       rbits[r] = hbn::bitlen(Np, x.nl);
+      if (nadic_early) nadic_consts(Np, x.nl, NAD + r * kNadicStride);
     }
   });
   uint32_t recvn_max = 1;
@@ -426,6 +469,8 @@ int prestart_ga(Ctx* c, const fsdkr_collect_batch* bs, uint32_t count, uint32_t*
                        group == kWideGroup ? "collect_ga_nn_w" : "collect_ga_nn", group == kWideGroup ? kWideGroup : 0u);
     return r;
   };
+  // the N-adic constants lie before the pair rows: they go up with the moduli
+  const uint32_t* d_nadic = nadic_early ? reinterpret_cast<const uint32_t*>(dev + o_nad) : nullptr;
   if (overlap) {
     if ((rc = c->hip_check(hipMemcpyAsync(dev, img, o_s2, hipMemcpyHostToDevice, gs), "prestart H2D moduli")) ||
         (rc = setup()))
@@ -495,6 +540,8 @@ int prestart_ga(Ctx* c, const fsdkr_collect_batch* bs, uint32_t count, uint32_t*
   g.split = ga_split_ok(nn, group, flags);
   SplitArgs head;
   head.lo_bit = kGaSplit;
+  if (g.split && d_nadic && ga_nadic_ok(c, nn, nl, group, flags)) g.nadic = d_nadic;
+  head.nadic = g.nadic;
   if ((rc = launch_modexp_desc(c, nn, (uint32_t)J1.size(), recvn_max, dev + o_desc, cons, g.out, gs, "mxt_GApre", gprio, group,
                                flags, g.split ? &head : nullptr)))
     return fail_sync(rc);

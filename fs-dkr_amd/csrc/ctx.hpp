@@ -281,7 +281,14 @@ struct SplitArgs {
   uint32_t lo_bit = 0;
   bool tail = false;
   const uint8_t* d_desc2 = nullptr;
+  // device rows of nadic_consts per modulus: the head runs in half-width N-adic
+  // form (modexp_nadic_head_kernel) and the tail takes over from it; head and
+  // tail of one chain are launched with the same setting
+  const uint32_t* nadic = nullptr;
 };
+// The N-adic head's constants of one modulus N (nl <= 64 limbs, odd): kNadicStride
+// words (kernels.h).  ~0.1 ms of host arithmetic.
+void nadic_consts(const uint32_t* N, uint32_t nl, uint32_t* out);
 int launch_modexp_desc(Ctx* c, uint32_t k32, uint32_t count, uint32_t exp_bits, const uint8_t* d_desc,
                        const uint32_t* d_consts, uint32_t* d_out, hipStream_t st = nullptr,
                        const char* table_tag = "mxtable", uint32_t prio = 0, uint32_t group = 0,

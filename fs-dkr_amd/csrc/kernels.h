@@ -52,7 +52,19 @@ struct ModexpArgs {
   const uint64_t* exp2_ptr = nullptr;    // [count]
   const uint32_t* exp2_len = nullptr;    // [count] limbs, exp2 < 2^lo_bit
   uint32_t* table2 = nullptr;       // [count][16][KD]
+  // N-adic head (modexp_nadic_head_kernel; 4096-bit class N^2 of a 2048-bit N, 16
+  // lanes, window 7): rows of kNadicStride words per modulus (nadic_consts, host).
+  // The head then leaves the raw pair (x0 | x1) in state, and the tail launched with
+  // the same pointer converts it and runs the low bits of exp over its own
+  // 16-entry table of base powers (built in `table`) instead of the head's table.
+  const uint32_t* nadic = nullptr;
 };
+
+// Per-modulus constants of the N-adic head, 72 digits of 29 bits each unless noted:
+// N' = N k0 (k0 = -N^-1 mod 2^29) | r | (N' - q) mod N' with (q, r) = divmod(R^2 mod
+// N'^2, N'), R = 2^(29*72) | C1 = R^3 mod N^2 (144 digits) | C2 = -N' C1 mod N^2 (144)
+constexpr int kNadicNp = 0, kNadicR0 = 72, kNadicR1 = 144, kNadicC1 = 216, kNadicC2 = 360, kNadicStride = 512;
+constexpr uint32_t kNadicWindow = 7;
 
 int shape_digits(uint32_t k32);   // KD for a K32-limb modulus class (0 if unsupported)
 // The 32-lane 4096-bit latency shape uses KD = 160 digits (L = 5 per lane), so its

@@ -515,6 +515,180 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_slide_kernel(const ModexpArgs
   for (int k = 0; k < LO; ++k) O[g * LO + k] = limb_of(stream, KD, g * LO + k);
 }
 
+// The head of a split chain modulo N^2 for a known 2048-bit N, in half-width
+// N-adic Montgomery form (ModexpArgs.nadic).  A residue X mod N'^2 (N' = N k0, the
+// quotient-scaled modulus of the 72-digit rows; N^2 | N'^2) is the pair (x0, x1),
+// X = x0 - x1 N', held by the chain's 16 lanes as two 8-lane groups: A (lanes
+// 0-7) x0 and B (lanes 8-15) x1, 9 digits per lane; state and table rows stay 144
+// words, x0's digits first.  With red(T) = (t, M), T + M N' = t R (R = 2^(29*72)):
+//   (a0,a1) (b0,b1) / R = (t, h),  (t, M) = red(a0 b0),  h = red(a0 b1 + a1 b0 + M)
+// (a0 b0 = t R - M N', and N' u / R mod N'^2 depends on u / R mod N' only).  Both
+// groups stream a0 from LDS and run the same rows (Mont29::product_pair):
+//   squaring       one pass:  A: b = x0, B: b = 2 x1, coupled (lane 8 takes M's digits)
+//   times (y0,y1)  pass 1 streams y0:     A: b = x0, B: b = x1, coupled
+//                  pass 2 streams old x0: B: b = y1 (A's result unused); x1 = h1 + h2
+// so a squaring is 72 rows of 18 MACs against 144 rows of 14 in the full-width
+// chain.  x0 stays < N' (1 + 2^-6) + 2 and x1 below twice that (R >= 2^11 N').
+// The schedule is modexp_slide_kernel's head: wave-uniform sliding windows of
+// kNadicWindow bits over the exponent bits >= lo_bit.  The raw pair goes to
+// state; the tail (modexp_tail_kernel NA) brings it into its full-width form.
+__global__ __launch_bounds__(BLOCK) void modexp_nadic_head_kernel(const ModexpArgs a) {
+  using MT = Mont29<72, 8>;
+  constexpr int L = MT::L, KD = 144, G = 16;
+  constexpr int IPB = BLOCK / G;
+  __shared__ uint32_t lds[IPB * KD];
+  const int g = threadIdx.x % G;
+  const int li = threadIdx.x / G;
+  const uint32_t inst = blockIdx.x * (blockDim.x / G) + li;
+  if (inst >= a.count) return;
+  if (a.prio == 1) __builtin_amdgcn_s_setprio(1);
+  else if (a.prio == 2) __builtin_amdgcn_s_setprio(2);
+  else if (a.prio >= 3) __builtin_amdgcn_s_setprio(3);
+  uint32_t* stream = lds + li * KD;
+  const uint32_t* C = a.nadic + (size_t)a.mod_idx[inst] * kNadicStride;
+  const bool hi = g >= 8;
+  uint32_t sh_hi = hi ? 1u : 0u, m_hi = hi ? 0xFFFFFFFFu : 0u;
+  asm volatile("" : "+v"(sh_hi), "+v"(m_hi));
+  MT M;
+  M.init_pair(g);
+#pragma unroll
+  for (int j = 0; j < L; ++j) M.n[j] = C[kNadicNp + (g & 7) * L + j];
+  M.ninv = 1u;
+  const uint32_t tw = 1u << (kNadicWindow - 1);
+  uint32_t* T = a.table + (size_t)inst * (tw + 1) * KD;
+  const uint64_t ea = a.exp_ptr[inst];
+  const uint32_t* E = reinterpret_cast<const uint32_t*>(
+      ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ea >> 32)) << 32) |
+      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ea));
+  const int exp_limbs = __builtin_amdgcn_readfirstlane((int)a.exp_len[inst]);
+  auto bit = [&](int i) -> uint32_t { return (E[i >> 5] >> (i & 31)) & 1u; };
+  int top = 32 * exp_limbs - 1;
+  while (top >= 0 && E[top >> 5] == 0) top = (top & ~31) - 1;
+  while (top >= 0 && !bit(top)) --top;
+  const int lo = (int)a.lo_bit;
+  auto window = [&](int i, int* jl) -> uint32_t {
+    int j = max(i - (int)kNadicWindow + 1, lo);
+    while (!bit(j)) ++j;
+    uint32_t d = 0;
+    for (int k = i; k >= j; --k) d = (d << 1) | bit(k);
+    *jl = j;
+    return d;   // odd
+  };
+  uint32_t acc[L];
+#pragma unroll
+  for (int j = 0; j < L; ++j) acc[j] = 0u;
+  const uint32_t* B = reinterpret_cast<const uint32_t*>(a.base_ptr[inst]);
+  const int blen = (int)min(a.base_len[inst], 64u);
+  auto load = [&](const uint32_t* row) {
+#pragma unroll
+    for (int j = 0; j < L; ++j) acc[j] = row[g * L + j];
+  };
+  auto store = [&](uint32_t* row) {
+#pragma unroll
+    for (int j = 0; j < L; ++j) row[g * L + j] = acc[j];
+  };
+  const bool none = top < lo;   // no bits for the head: the pair of 1 (Montgomery form)
+  // phase 0: x = (base, 0) M(R);  1: x^2;  2: T[jt] = T[jt-1] x^2;  3: the windows
+  int phase = 0, i = top, pend_mul = -1;
+  uint32_t jt = 1, pend_sq = 0;
+  for (;;) {
+    if (phase == 3) {
+      if (pend_sq == 0 && pend_mul < 0)
+        while (i >= lo && !bit(i)) {
+          ++pend_sq;
+          --i;
+        }
+      for (; pend_sq; --pend_sq) {   // the squarings between two products, in a loop of their own
+        __builtin_amdgcn_wave_barrier();
+        lds_put<KD, G>(stream, acc, g);
+        __builtin_amdgcn_wave_barrier();
+        uint32_t b[L];
+#pragma unroll
+        for (int j = 0; j < L; ++j) b[j] = acc[j] << sh_hi;
+        M.product_pair<true>(acc, b, stream);
+      }
+    }
+    const uint32_t* src = nullptr;
+    if (phase == 2) {
+      src = T + (size_t)tw * KD;
+    } else if (phase == 3) {
+      if (pend_mul >= 0) {
+        src = T + (size_t)pend_mul * KD;
+        pend_mul = -1;
+      } else if (i < lo) {
+        break;
+      } else {   // bit i is set: its window's squarings, then its product
+        int jl;
+        const uint32_t d = window(i, &jl);
+        pend_sq = (uint32_t)(i - jl + 1);
+        pend_mul = (int)(d >> 1);
+        i = jl - 1;
+        continue;
+      }
+    }
+    // one coupled pass: the entry product, x^2, or pass 1 of a table product
+    uint32_t b[L], y[L];
+    __builtin_amdgcn_wave_barrier();
+    if (phase == 0) {
+#pragma unroll
+      for (int j = 0; j < L; ++j) {
+        const int d = g * L + j;
+        b[j] = C[kNadicR0 + d];   // r in group A, (N' - q) in group B
+        if (!hi) stream[d] = none ? (d == 0 ? 1u : 0u) : digit_of(B, blen, d);
+      }
+    } else if (phase == 1) {
+      lds_put<KD, G>(stream, acc, g);
+#pragma unroll
+      for (int j = 0; j < L; ++j) b[j] = acc[j] << sh_hi;
+    } else {
+#pragma unroll
+      for (int j = 0; j < L; ++j) {
+        y[j] = src[g * L + j];
+        b[j] = acc[j];
+      }
+      if (!hi) {   // y0 for pass 1, the old x0 for pass 2
+#pragma unroll
+        for (int j = 0; j < L; ++j) {
+          stream[g * L + j] = y[j];
+          stream[72 + g * L + j] = acc[j];
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    M.product_pair<true>(b, b, stream);
+    if (src) {   // pass 2: B: old x0 * y1, uncoupled (A's operand only has to be bounded)
+#pragma unroll
+      for (int j = 0; j < L; ++j) y[j] = hi ? y[j] : acc[j];
+      M.product_pair<false>(y, y, stream + 72);
+#pragma unroll
+      for (int j = 0; j < L; ++j) acc[j] = b[j] + (y[j] & m_hi);
+    } else {
+#pragma unroll
+      for (int j = 0; j < L; ++j) acc[j] = b[j];
+    }
+    if (phase == 0) {
+      if (none) break;
+      store(T);
+      phase = 1;
+    } else if (phase == 1) {
+      store(T + (size_t)tw * KD);
+      load(T);
+      phase = tw > 1 ? 2 : 3;
+    } else if (phase == 2) {
+      store(T + (size_t)jt * KD);
+      if (++jt == tw) phase = 3;
+    }
+    if (phase == 3 && i == top) {   // the first window: its odd power, no squarings of 1
+      int jl;
+      const uint32_t d = window(i, &jl);
+      load(T + (size_t)(d >> 1) * KD);
+      i = jl - 1;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < L; ++j) a.state[(size_t)inst * KD + g * L + j] = acc[j];
+}
+
 // The tail of a split chain (ModexpArgs lo_bit / tail): resumes the head's
 // accumulator x^(E >> lo) and runs the exponent bits below lo with the head's
 // sliding windows (wave-uniform E, the head's odd-power table), and with base2 set
@@ -525,7 +699,7 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_slide_kernel(const ModexpArgs
 // (zk_pdl_with_slack.rs:136-142 via commitment_unknown_order :170-188,
 // range_proofs.rs:140-148).  QS as the head (the 8 / 16-lane shapes quotient-
 // scaled, the 4-lane throughput shape plain).  Exact results.
-template <int KD, int G, int K32, bool QS>
+template <int KD, int G, int K32, bool QS, bool NA = false>
 __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs a) {
   using MT = Mont29<KD, G>;
   constexpr int L = MT::L;
@@ -553,7 +727,7 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs 
     else M.mul(x, x, stream);
   };
   const uint32_t w = a.window, tw = 1u << (w - 1);
-  const uint32_t* T = a.table + (size_t)inst * (tw + 1) * KD;
+  uint32_t* T = a.table + (size_t)inst * (tw + 1) * KD;
   const uint64_t ea = a.exp_ptr[inst];
   const uint32_t* E = reinterpret_cast<const uint32_t*>(
       ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ea >> 32)) << 32) |
@@ -570,6 +744,52 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs 
     for (int j = 0; j < L; ++j) stream[g * L + j] = row[g * L + j];
     __builtin_amdgcn_wave_barrier();
   };
+  if constexpr (NA) {
+    // the N-adic head left the raw pair (x0 | x1), X = x0 - x1 N' = x R_half: into
+    // this chain's form as Y = x0 C1 / R + x1 C2 / R = x R (mod N^2), Y < 2 (N^2)'
+    // (C1 = R_half^3, C2 = -N' C1 mod N^2); then T[u] = base^u, u < 16, over the
+    // head's table rows: the exponent's low bits run as 4-bit fixed windows
+    static_assert(KD == 144 && G == 16 && QS, "the N-adic head's shape");
+    const uint32_t* CN = a.nadic + (size_t)a.mod_idx[inst] * kNadicStride;
+    uint32_t y[L];
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+      stream[g * L + j] = g < 8 ? acc[j] : 0u;   // x0, zero-extended
+      y[j] = CN[kNadicC1 + g * L + j];
+    }
+    __builtin_amdgcn_wave_barrier();
+    mulx(y);
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < L; ++j) stream[(g ^ 8) * L + j] = g >= 8 ? acc[j] : 0u;   // x1 moves down to the low digits
+#pragma unroll
+    for (int j = 0; j < L; ++j) acc[j] = CN[kNadicC2 + g * L + j];
+    __builtin_amdgcn_wave_barrier();
+    mulx(acc);
+#pragma unroll
+    for (int j = 0; j < L; ++j) acc[j] += y[j];
+    M.carry_exact(acc);   // digits of a sum back to < 2^29 (the squarings double them)
+    const uint32_t* B = reinterpret_cast<const uint32_t*>(a.base_ptr[inst]);
+    const int blen = (int)min(a.base_len[inst], (uint32_t)K32);
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+      y[j] = digit_of(B, blen, g * L + j);
+      T[g * L + j] = C[KD + g * L + j];   // T[0] = 1
+    }
+    put_row(C + 2 * KD);
+    mulx(y);
+#pragma unroll
+    for (int j = 0; j < L; ++j) T[KD + g * L + j] = y[j];
+    __builtin_amdgcn_wave_barrier();
+    lds_put<KD, G>(stream, y, g);
+    __builtin_amdgcn_wave_barrier();
+    for (int u = 2; u < 16; ++u) {
+      mulx(y);
+#pragma unroll
+      for (int j = 0; j < L; ++j) T[(size_t)u * KD + g * L + j] = y[j];
+    }
+  }
   // the joint base's table T2[u] = base2^u (Montgomery form), u < 16
   const bool joint = a.base2_ptr != nullptr;
   uint32_t* T2 = joint ? a.table2 + (size_t)inst * 16 * KD : nullptr;
@@ -604,7 +824,7 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs 
   uint32_t pend_d = 0, ew = 0;
   for (int i = lo - 1; i >= 0; --i) {
     if ((i & 31) == 31 && joint) ew = ((uint32_t)(i >> 5) < e2len) ? E2[i >> 5] : 0u;
-    if (pend_at < 0 && bit(i)) {   // a window starts: its lowest set bit jl >= max(i - w + 1, 0)
+    if (!NA && pend_at < 0 && bit(i)) {   // a window starts: its lowest set bit jl >= max(i - w + 1, 0)
       int j = max(i - (int)w + 1, 0);
       while (!bit(j)) ++j;
       uint32_t d = 0;
@@ -617,10 +837,17 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs 
     __builtin_amdgcn_wave_barrier();
     if constexpr (QS) M.sqr_s(acc, acc, stream);
     else M.sqr(acc, acc, stream);
-    if (i == pend_at) {
+    if (!NA && i == pend_at) {
       put_row(T + (size_t)(pend_d >> 1) * KD);
       mulx(acc);
       pend_at = -1;
+    }
+    if (NA && (i & 3) == 0) {   // the exponent's own 4-bit digit (wave-uniform: a zero digit is skipped)
+      const uint32_t d = (i >> 5) < exp_limbs ? (E[i >> 5] >> (i & 31)) & 15u : 0u;
+      if (d) {
+        put_row(T + (size_t)d * KD);
+        mulx(acc);
+      }
     }
     if (joint && (i & 3) == 0) {
       put_row(T2 + (size_t)((ew >> (i & 31)) & 15u) * KD);
@@ -781,13 +1008,22 @@ static hipError_t launch_modexp_slide(const ModexpArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-template <int KD, int G, int K32, bool QS>
+static hipError_t launch_modexp_nadic_head(const ModexpArgs& a, hipStream_t st) {
+  const uint32_t bs = block_threads(a.count * 16);
+  const uint32_t ipb = bs / 16;
+  const uint32_t blocks = (a.count + ipb - 1) / ipb;
+  if (blocks == 0) return hipSuccess;
+  hipLaunchKernelGGL(modexp_nadic_head_kernel, dim3(blocks), dim3(bs), 0, st, a);
+  return hipGetLastError();
+}
+
+template <int KD, int G, int K32, bool QS, bool NA = false>
 static hipError_t launch_modexp_tail(const ModexpArgs& a, hipStream_t st) {
   const uint32_t bs = block_threads(a.count * G);
   const uint32_t ipb = bs / G;
   const uint32_t blocks = (a.count + ipb - 1) / ipb;
   if (blocks == 0) return hipSuccess;
-  hipLaunchKernelGGL((modexp_tail_kernel<KD, G, K32, QS>), dim3(blocks), dim3(bs), 0, st, a);
+  hipLaunchKernelGGL((modexp_tail_kernel<KD, G, K32, QS, NA>), dim3(blocks), dim3(bs), 0, st, a);
   return hipGetLastError();
 }
 
@@ -889,6 +1125,10 @@ hipError_t modexp(uint32_t k32, const ModexpArgs& a, hipStream_t st) {
       return launch_modexp_slide<160, 32, 128, true>(a, st);
     }
     if (a.lo_bit) {   // split chains: head and tail at the caller's lanes, QS as the full chain's
+      if (a.nadic) {   // the half-width N-adic head and the tail that takes over from it
+        if (a.group != 16 || a.window != kNadicWindow || !a.state) return hipErrorInvalidValue;
+        return a.tail ? launch_modexp_tail<144, 16, 128, true, true>(a, st) : launch_modexp_nadic_head(a, st);
+      }
       switch (a.group) {
         case 16: return a.tail ? launch_modexp_tail<144, 16, 128, true>(a, st)
                                : launch_modexp_slide<144, 16, 128, true>(a, st);

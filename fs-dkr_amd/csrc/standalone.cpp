@@ -283,51 +283,58 @@ int fsdkr_ring_pedersen_verify(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, uint
 // out[i] = base[i]^E[mod_idx[i]] * base2[i]^exp2[i] mod N[mod_idx[i]] through the
 // split chains of collect()'s GA (head over E's bits >= 256, joint tail), for
 // parity tests of that path (modexp.hip modexp_tail_kernel).
-int fsdkr_modexp_joint_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* base, const uint32_t* base2,
-                             const uint32_t* exp2, const uint32_t* mod_idx, const uint32_t* mods,
-                             const uint32_t* mod_exp, uint32_t exp_limbs, uint32_t n_mod, uint32_t* out) {
-  Ctx* c = reinterpret_cast<Ctx*>(ctx);
-  if (!c) return FSDKR_E_ARG;
-  if (count == 0) return FSDKR_OK;
+//
+// nmods (fsdkr_modexp_nadic_batch): the moduli are N^2 of these n_mod odd N of 64
+// limbs and the bases have KB = 64 limbs: the head runs in half-width N-adic form
+// (modexp.hip modexp_nadic_head_kernel) at 16 lanes, the tail takes over from it.
+static int joint_batch_impl(Ctx* c, const char* who, uint32_t count, const uint32_t* base, uint32_t KB,
+                            const uint32_t* base2, const uint32_t* exp2, const uint32_t* mod_idx, const uint32_t* mods,
+                            const uint32_t* nmods, const uint32_t* mod_exp, uint32_t exp_limbs, uint32_t n_mod,
+                            uint32_t* out) {
   constexpr uint32_t K = 128, E2L = 8, LO = 256;
   if (!base || !base2 || !exp2 || !mod_idx || !mods || !mod_exp || !out || !n_mod || !exp_limbs) {
-    c->fail("fsdkr_modexp_joint_batch: null pointer or empty table");
+    c->fail("%s: null pointer or empty table", who);
     return FSDKR_E_ARG;
   }
   uint32_t ebits = 1;
   for (uint32_t m = 0; m < n_mod; ++m) {
     if ((mods[(size_t)m * K] & 1u) == 0) {
-      c->fail("fsdkr_modexp_joint_batch: modulus %u is even", m);
+      c->fail("%s: modulus %u is even", who, m);
       return FSDKR_E_ARG;
     }
     ebits = std::max(ebits, bit_len(mod_exp + (size_t)m * exp_limbs, exp_limbs));
   }
   for (uint32_t i = 0; i < count; ++i)
     if (mod_idx[i] >= n_mod) {
-      c->fail("fsdkr_modexp_joint_batch: mod_idx[%u] out of range", i);
+      c->fail("%s: mod_idx[%u] out of range", who, i);
       return FSDKR_E_ARG;
     }
-  const uint32_t group = (c->modexp_group == 8 || c->modexp_group == 4 || c->modexp_group == kWideGroup)
+  const uint32_t group = nmods ? 16u
+                         : (c->modexp_group == 8 || c->modexp_group == 4 || c->modexp_group == kWideGroup)
                              ? c->modexp_group : 16u,
                  per_wave = 64 / group;
-  const size_t o_b = 0, o_b2 = al256((size_t)count * K * 4), o_e2 = o_b2 + al256((size_t)count * K * 4),
+  if (nmods && (c->ct || (c->modexp_group && c->modexp_group != 16))) {
+    c->fail("%s: the N-adic head runs at 16 lanes, public exponents", who);
+    return FSDKR_E_ARG;
+  }
+  const size_t o_b = 0, o_b2 = al256((size_t)count * KB * 4), o_e2 = o_b2 + al256((size_t)count * K * 4),
                o_m = o_e2 + al256((size_t)count * E2L * 4), o_me = o_m + al256((size_t)n_mod * K * 4),
                o_out = o_me + al256((size_t)n_mod * exp_limbs * 4), o_desc = o_out + al256(((size_t)count + 1) * K * 4);
   const size_t cap = (size_t)count + (size_t)n_mod * per_wave;   // instances + pads
   const size_t o_desc2 = o_desc + al256(cap * 36), total = o_desc2 + al256(cap * 20);
   uint8_t* dev = (uint8_t*)c->buf("mxj", total);
   if (!dev) {
-    c->fail("fsdkr_modexp_joint_batch: device allocation failed");
+    c->fail("%s: device allocation failed", who);
     return FSDKR_E_OOM;
   }
   auto DI = [&](size_t o) { return (uint64_t)(uintptr_t)(dev + o); };
   ModexpJob J;
   J.k32 = K;
   for (uint32_t i = 0; i < count; ++i)
-    J.add(DI(o_b + (size_t)i * K * 4), K, DI(o_me + (size_t)mod_idx[i] * exp_limbs * 4), exp_limbs, ebits, mod_idx[i]);
+    J.add(DI(o_b + (size_t)i * KB * 4), KB, DI(o_me + (size_t)mod_idx[i] * exp_limbs * 4), exp_limbs, ebits, mod_idx[i]);
   const bool aligned = group_by_exponent(J, per_wave, count);
   if (!aligned) {
-    c->fail("fsdkr_modexp_joint_batch: instances not wave-uniform");
+    c->fail("%s: instances not wave-uniform", who);
     return FSDKR_E_ARG;
   }
   std::vector<uint8_t> desc;
@@ -348,7 +355,7 @@ int fsdkr_modexp_joint_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* bas
   auto up = [&](size_t o, const void* src, size_t bytes) {
     return c->hip_check(hipMemcpyAsync(dev + o, src, bytes, hipMemcpyHostToDevice, c->stream), "H2D joint");
   };
-  if ((rc = up(o_b, base, (size_t)count * K * 4)) || (rc = up(o_b2, base2, (size_t)count * K * 4)) ||
+  if ((rc = up(o_b, base, (size_t)count * KB * 4)) || (rc = up(o_b2, base2, (size_t)count * K * 4)) ||
       (rc = up(o_e2, exp2, (size_t)count * E2L * 4)) || (rc = up(o_m, mods, (size_t)n_mod * K * 4)) ||
       (rc = up(o_me, mod_exp, (size_t)n_mod * exp_limbs * 4)) || (rc = up(o_desc, desc.data(), desc.size())) ||
       (rc = up(o_desc2, desc2.data(), desc2.size())))
@@ -360,6 +367,19 @@ int fsdkr_modexp_joint_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* bas
   const uint32_t flags = ga_desc_flags(true, group);
   SplitArgs head;
   head.lo_bit = LO;
+  std::vector<uint32_t> nadic;
+  if (nmods) {
+    nadic.resize((size_t)n_mod * kNadicStride);
+    for (uint32_t m = 0; m < n_mod; ++m) nadic_consts(nmods + (size_t)m * 64, 64, nadic.data() + (size_t)m * kNadicStride);
+    uint32_t* dn = (uint32_t*)c->buf("mxj_nadic", nadic.size() * 4);
+    if (!dn) {
+      c->fail("%s: device allocation failed", who);
+      return FSDKR_E_OOM;
+    }
+    if ((rc = c->hip_check(hipMemcpyAsync(dn, nadic.data(), nadic.size() * 4, hipMemcpyHostToDevice, c->stream), "H2D N-adic")))
+      return rc;
+    head.nadic = dn;
+  }
   SplitArgs tail = head;
   tail.tail = true;
   tail.d_desc2 = dev + o_desc2;
@@ -372,6 +392,36 @@ int fsdkr_modexp_joint_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* bas
   if ((rc = c->hip_check(hipMemcpyAsync(out, d_out, (size_t)count * K * 4, hipMemcpyDeviceToHost, c->stream), "D2H")))
     return rc;
   return c->sync();
+}
+
+
+int fsdkr_modexp_joint_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* base, const uint32_t* base2,
+                             const uint32_t* exp2, const uint32_t* mod_idx, const uint32_t* mods,
+                             const uint32_t* mod_exp, uint32_t exp_limbs, uint32_t n_mod, uint32_t* out) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return FSDKR_E_ARG;
+  if (count == 0) return FSDKR_OK;
+  return joint_batch_impl(c, "fsdkr_modexp_joint_batch", count, base, 128, base2, exp2, mod_idx, mods, nullptr, mod_exp,
+                          exp_limbs, n_mod, out);
+}
+
+int fsdkr_modexp_nadic_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* base, const uint32_t* base2,
+                             const uint32_t* exp2, const uint32_t* mod_idx, const uint32_t* nmods,
+                             const uint32_t* mod_exp, uint32_t exp_limbs, uint32_t n_mod, uint32_t* out) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return FSDKR_E_ARG;
+  if (count == 0) return FSDKR_OK;
+  if (!nmods || !n_mod) {
+    c->fail("fsdkr_modexp_nadic_batch: null pointer or empty table");
+    return FSDKR_E_ARG;
+  }
+  std::vector<uint32_t> sq((size_t)n_mod * 128);
+  for (uint32_t m = 0; m < n_mod; ++m) {
+    const hbn::Limbs N = hbn::from(nmods + (size_t)m * 64, 64);
+    hbn::store(hbn::mul(N, N), sq.data() + (size_t)m * 128, 128);
+  }
+  return joint_batch_impl(c, "fsdkr_modexp_nadic_batch", count, base, 64, base2, exp2, mod_idx, sq.data(), nmods, mod_exp,
+                          exp_limbs, n_mod, out);
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@ FSDKR_CFG_TIMING = 1
 FSDKR_CFG_FB_BGMW = 2    # fixed-base exponentiations by BGMW windows only
 FSDKR_CFG_FB_COMB = 4    # a Lim-Lee comb wherever one fits
 FSDKR_CFG_INV_EACH = 8   # one inverse per element (no simultaneous inversion)
+FSDKR_CFG_GA_FULLWIDTH = 16   # GA's head as a generic 4096-bit chain (not half-width N-adic)
 
 u32p = ctypes.POINTER(ctypes.c_uint32)
 
@@ -130,6 +131,8 @@ def lib():
     L.fsdkr_modexp_joint_batch.argtypes = [vp, ctypes.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p, ctypes.c_uint32,
                                            ctypes.c_uint32, u32p]
     L.fsdkr_modexp_joint_batch.restype = ctypes.c_int
+    L.fsdkr_modexp_nadic_batch.argtypes = L.fsdkr_modexp_joint_batch.argtypes
+    L.fsdkr_modexp_nadic_batch.restype = ctypes.c_int
     L.fsdkr_modexp_batch_ct.restype = ctypes.c_int
     L.fsdkr_modexp_batch_device.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, ctypes.c_uint32,
                                             ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp]
@@ -306,6 +309,25 @@ class Context:
         O = np.zeros((count, 128), dtype=np.uint32)
         self.check(self._lib.fsdkr_modexp_joint_batch(self._h, count, _ptr(B), _ptr(B2), _ptr(E2), _ptr(I), _ptr(Mo),
                                                       _ptr(ME), exp_limbs, len(mods), _ptr(O)))
+        return limbs_to_ints(O)
+
+    def modexp_nadic_batch(self, bases, bases2, exps2, nmods, mod_exps, mod_idx):
+        """[bases[i] ^ mod_exps[k] * bases2[i] ^ exps2[i] mod nmods[k]^2], k = mod_idx[i], for
+        odd nmods and bases below 2^2048: the half-width N-adic head of collect()'s GA
+        chains and the tail that takes over from it (fsdkr_modexp_nadic_batch)."""
+        count = len(bases)
+        if count == 0:
+            return []
+        exp_limbs = max(1, (max(e.bit_length() for e in mod_exps) + 31) // 32)
+        B = ints_to_limbs(bases, 64)
+        B2 = ints_to_limbs(bases2, 128)
+        E2 = ints_to_limbs(exps2, 8)
+        Mo = ints_to_limbs(nmods, 64)
+        ME = ints_to_limbs(mod_exps, exp_limbs)
+        I = np.ascontiguousarray(np.asarray(mod_idx, dtype=np.uint32))
+        O = np.zeros((count, 128), dtype=np.uint32)
+        self.check(self._lib.fsdkr_modexp_nadic_batch(self._h, count, _ptr(B), _ptr(B2), _ptr(E2), _ptr(I), _ptr(Mo),
+                                                      _ptr(ME), exp_limbs, len(nmods), _ptr(O)))
         return limbs_to_ints(O)
 
     def fixed_base_modexp(self, bases, base_mod_idx, mods, base_idx, exps, mod_limbs):

@@ -46,10 +46,13 @@ typedef struct fsdkr_cfg {
  * under every setting; the default (0) is the fastest measured.
  *   FB_BGMW   fixed-base exponentiations by BGMW windows only (no Lim-Lee comb)
  *   FB_COMB   a Lim-Lee comb wherever one fits, even where it saves nothing
- *   INV_EACH  one binary-GCD inverse per element (no simultaneous inversion) */
+ *   INV_EACH  one binary-GCD inverse per element (no simultaneous inversion)
+ *   GA_FULLWIDTH  the s^N mod N^2 chains of collect() run their head as a generic
+ *             4096-bit Montgomery chain, not in half-width N-adic form */
 #define FSDKR_CFG_FB_BGMW 2u
 #define FSDKR_CFG_FB_COMB 4u
 #define FSDKR_CFG_INV_EACH 8u
+#define FSDKR_CFG_GA_FULLWIDTH 16u
 
 /* Context: owns the HIP stream, device buffers and per-modulus constant
  * tables.  Replaces nothing in the reference (which holds no state between
@@ -299,6 +302,16 @@ int fsdkr_collect_prestart(fsdkr_ctx* ctx, const fsdkr_collect_batch* batch);
  * with base2 = c^-1.  Parity tests of that path; odd moduli. */
 int fsdkr_modexp_joint_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* base, const uint32_t* base2,
                              const uint32_t* exp2, const uint32_t* mod_idx, const uint32_t* mods,
+                             const uint32_t* mod_exp, uint32_t exp_limbs, uint32_t n_mod, uint32_t* out);
+
+/* The same product for moduli N^2 of known odd N (nmods: n_mod rows of 64 limbs)
+ * and bases of 64 limbs, the shape of collect()'s 2048-bit receivers: the head runs in
+ * half-width N-adic Montgomery form (a residue X mod N'^2 as x0 - x1 N', N' = N times
+ * (-N^-1 mod 2^29); a squaring is one pass of 72 rows instead of 144) at 16 lanes,
+ * the tail takes over in full width.  out: 128 limbs per instance, equal to
+ * fsdkr_modexp_joint_batch on the zero-extended inputs.  Parity tests of that path. */
+int fsdkr_modexp_nadic_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* base, const uint32_t* base2,
+                             const uint32_t* exp2, const uint32_t* mod_idx, const uint32_t* nmods,
                              const uint32_t* mod_exp, uint32_t exp_limbs, uint32_t n_mod, uint32_t* out);
 
 /* Which prestarted parts the last fsdkr_collect_prepare[_multi] reused (bit
