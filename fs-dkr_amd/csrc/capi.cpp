@@ -396,6 +396,17 @@ int launch_modexp_desc(Ctx* c, uint32_t k32, uint32_t count, uint32_t exp_bits, 
         c->fail("device allocation failed (joint table)");
         return FSDKR_E_OOM;
       }
+      if (split->d_desc3) {
+        a.base3_ptr = reinterpret_cast<const uint64_t*>(split->d_desc3);
+        a.exp3_ptr = reinterpret_cast<const uint64_t*>(split->d_desc3 + n8);
+        a.exp3_len = reinterpret_cast<const uint32_t*>(split->d_desc3 + 2 * n8);
+        a.exp3_bits = split->exp3_bits;
+        a.table3 = (uint32_t*)c->buf((base + "_t3").c_str(), (size_t)count * 16 * KD * 4);
+        if (!a.table3) {
+          c->fail("device allocation failed (joint table)");
+          return FSDKR_E_OOM;
+        }
+      }
     }
   }
   const size_t tm = c->tbeg("modexp", st);

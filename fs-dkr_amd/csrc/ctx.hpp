@@ -285,6 +285,10 @@ struct SplitArgs {
   // form (modexp_nadic_head_kernel) and the tail takes over from it; head and
   // tail of one chain are launched with the same setting
   const uint32_t* nadic = nullptr;
+  // a second extra base of the tail (ModexpArgs base3_ptr): descriptors laid out as
+  // d_desc2's, exp3 < 2^exp3_bits for every instance; needs d_desc2, not nadic
+  const uint8_t* d_desc3 = nullptr;
+  uint32_t exp3_bits = 0;
 };
 // The N-adic head's constants of one modulus N (nl <= 64 limbs, odd): kNadicStride
 // words (kernels.h).  ~0.1 ms of host arithmetic.

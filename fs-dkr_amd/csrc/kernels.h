@@ -58,6 +58,17 @@ struct ModexpArgs {
   // the same pointer converts it and runs the low bits of exp over its own
   // 16-entry table of base powers (built in `table`) instead of the head's table.
   const uint32_t* nadic = nullptr;
+  // A second extra base of the tail (modexp_tail_kernel J3; needs base2_ptr, not the
+  // N-adic head): out = base^exp * base2^exp2 * base3^exp3, base3 read as base2 is,
+  // 4-bit windows of exp3 < 2^exp3_bits over a 16-entry table in table3.  exp3_bits
+  // (a multiple of 4, <= lo_bit) is the launch's bound: the windows above it are
+  // skipped for every instance.  Bob's MtA range proof (range_proofs.rs:396-400):
+  // s^N * a_enc^s1 * (mta^-1)^e mod N^2 in one chain, lo_bit = 768, exp3_bits = 256.
+  const uint64_t* base3_ptr = nullptr;   // [count] K32 limbs, reduced
+  const uint64_t* exp3_ptr = nullptr;    // [count]
+  const uint32_t* exp3_len = nullptr;    // [count] limbs
+  uint32_t* table3 = nullptr;            // [count][16][KD]
+  uint32_t exp3_bits = 0;
 };
 
 // Per-modulus constants of the N-adic head, 72 digits of 29 bits each unless noted:

@@ -699,7 +699,9 @@ __global__ __launch_bounds__(BLOCK) void modexp_nadic_head_kernel(const ModexpAr
 // (zk_pdl_with_slack.rs:136-142 via commitment_unknown_order :170-188,
 // range_proofs.rs:140-148).  QS as the head (the 8 / 16-lane shapes quotient-
 // scaled, the 4-lane throughput shape plain).  Exact results.
-template <int KD, int G, int K32, bool QS, bool NA = false>
+// J3: a second extra base (ModexpArgs base3_ptr): base3^exp3 rides the same
+// squarings over its own 16-entry table, 4-bit windows of exp3 below exp3_bits.
+template <int KD, int G, int K32, bool QS, bool NA = false, bool J3 = false>
 __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs a) {
   using MT = Mont29<KD, G>;
   constexpr int L = MT::L;
@@ -818,12 +820,46 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs 
       for (int j = 0; j < L; ++j) T2[(size_t)u * KD + g * L + j] = y[j];
     }
   }
+  // the second extra base's table T3[u] = base3^u, u < 16
+  uint32_t* T3 = nullptr;
+  const uint32_t* E3 = nullptr;
+  uint32_t e3len = 0, ew3 = 0;
+  int e3bits = 0;
+  if constexpr (J3) {
+    static_assert(!NA, "the three-base tail follows the full-width head");
+    T3 = a.table3 + (size_t)inst * 16 * KD;
+    E3 = reinterpret_cast<const uint32_t*>(a.exp3_ptr[inst]);
+    e3len = a.exp3_len[inst];
+    e3bits = (int)a.exp3_bits;
+    const uint32_t* B3 = reinterpret_cast<const uint32_t*>(a.base3_ptr[inst]);
+    uint32_t y[L];
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+      y[j] = digit_of(B3, K32, g * L + j);
+      T3[g * L + j] = C[KD + g * L + j];
+    }
+    put_row(C + 2 * KD);
+    mulx(y);
+#pragma unroll
+    for (int j = 0; j < L; ++j) T3[KD + g * L + j] = y[j];
+    __builtin_amdgcn_wave_barrier();
+    lds_put<KD, G>(stream, y, g);
+    __builtin_amdgcn_wave_barrier();
+    for (int u = 2; u < 16; ++u) {
+      mulx(y);
+#pragma unroll
+      for (int j = 0; j < L; ++j) T3[(size_t)u * KD + g * L + j] = y[j];
+    }
+  }
   // bits lo-1 .. 0: square; the sliding window of E that ends at i multiplies
   // T[d >> 1] in; every 4th bit the instance's exp2 digit multiplies T2[digit] in
   int pend_at = -1;
   uint32_t pend_d = 0, ew = 0;
   for (int i = lo - 1; i >= 0; --i) {
     if ((i & 31) == 31 && joint) ew = ((uint32_t)(i >> 5) < e2len) ? E2[i >> 5] : 0u;
+    if constexpr (J3) {
+      if ((i & 31) == 31) ew3 = ((uint32_t)(i >> 5) < e3len) ? E3[i >> 5] : 0u;
+    }
     if (!NA && pend_at < 0 && bit(i)) {   // a window starts: its lowest set bit jl >= max(i - w + 1, 0)
       int j = max(i - (int)w + 1, 0);
       while (!bit(j)) ++j;
@@ -852,6 +888,12 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs 
     if (joint && (i & 3) == 0) {
       put_row(T2 + (size_t)((ew >> (i & 31)) & 15u) * KD);
       mulx(acc);
+    }
+    if constexpr (J3) {
+      if ((i & 3) == 0 && i < e3bits) {   // launch-uniform bound: no products above exp3's width
+        put_row(T3 + (size_t)((ew3 >> (i & 31)) & 15u) * KD);
+        mulx(acc);
+      }
     }
   }
   // exit: acc * 1 / R modulo N itself
@@ -1017,13 +1059,13 @@ static hipError_t launch_modexp_nadic_head(const ModexpArgs& a, hipStream_t st) 
   return hipGetLastError();
 }
 
-template <int KD, int G, int K32, bool QS, bool NA = false>
+template <int KD, int G, int K32, bool QS, bool NA = false, bool J3 = false>
 static hipError_t launch_modexp_tail(const ModexpArgs& a, hipStream_t st) {
   const uint32_t bs = block_threads(a.count * G);
   const uint32_t ipb = bs / G;
   const uint32_t blocks = (a.count + ipb - 1) / ipb;
   if (blocks == 0) return hipSuccess;
-  hipLaunchKernelGGL((modexp_tail_kernel<KD, G, K32, QS, NA>), dim3(blocks), dim3(bs), 0, st, a);
+  hipLaunchKernelGGL((modexp_tail_kernel<KD, G, K32, QS, NA, J3>), dim3(blocks), dim3(bs), 0, st, a);
   return hipGetLastError();
 }
 
@@ -1119,6 +1161,18 @@ hipError_t modexp(uint32_t k32, const ModexpArgs& a, hipStream_t st) {
   // exponents, interleaved, profiles/r05/r05qs4_*)
   if (a.slide) {   // shared exponent per wave: the 4096-bit shapes of GA
     if (k32 != 128 || a.ct || a.group == kWaveGroup) return hipErrorInvalidValue;
+    if (a.base3_ptr) {   // the three-base tail: after the full-width head, beside base2
+      if (!a.lo_bit || !a.tail || a.nadic || !a.base2_ptr || !a.exp3_ptr || !a.exp3_len || !a.table3 ||
+          (a.exp3_bits & 3u) || a.exp3_bits > a.lo_bit)
+        return hipErrorInvalidValue;
+      switch (a.group) {
+        case kWideGroup: return launch_modexp_tail<160, 32, 128, true, false, true>(a, st);
+        case 16: return launch_modexp_tail<144, 16, 128, true, false, true>(a, st);
+        case 8: return launch_modexp_tail<144, 8, 128, true, false, true>(a, st);
+        case 4: return launch_modexp_tail<144, 4, 128, true, false, true>(a, st);
+        default: return hipErrorInvalidValue;
+      }
+    }
     if (a.group == kWideGroup) {   // 32 lanes (KD = 160 constants, the caller's): small launches
       if (a.lo_bit && a.tail)
         return launch_modexp_tail<160, 32, 128, true>(a, st);

@@ -1,0 +1,566 @@
+// Bob's MtA range proofs of the C ABI (include/fsdkr/fsdkr.h):
+//   fsdkr_modexp_joint3_batch   parity entry of the three-base tail (modexp.hip modexp_tail_kernel J3)
+//   fsdkr_bob_verify            BobProof::verify (range_proofs.rs:360-446) and
+//                               BobProofExt::verify (:527-562), `count` proofs in one pass
+//   fsdkr_bob_verify_unfused    the same verdicts with three separate mod-N^2 chains (A/B)
+// Per proof, in the reference's order: s1 <= q^3 (:374); z^e, mta^e, t^e units
+// (:378-406); z' = h1^s1 h2^s2 z^-e, w = h1^t1 h2^t2 t^-e mod N~ (:385-388, :408-411);
+// v = a_enc^s1 s^N (1 + t1 N) mta^-e mod N^2 (:396-400); the transcript hash
+// (:413-441); with X / u the curve equation G s1 == X e + u (:550-559).
+// The pieces: fixed-base combs for the four h1 / h2 powers (bases shared per key),
+// a 256-bit modexp job for z^e | t^e, Montgomery's simultaneous inversion, and for
+// s^N a_enc^s1 (mta^-1)^e ONE split chain of 2048 squarings: the head over N's
+// bits >= 768, the tail with a_enc (4-bit windows of s1 < 2^768) and mta^-1
+// (windows of e < 2^256) riding its squarings.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "collect.hpp"
+#include "ctx.hpp"
+#include "fbjob.hpp"
+#include "fsdkr/fsdkr.h"
+#include "hostbn.hpp"
+#include "kernels.h"
+#include "verify.h"
+
+using namespace fsdkr;
+
+namespace {
+
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+uint32_t bit_len(const uint32_t* x, uint32_t limbs) {
+  for (int k = (int)limbs - 1; k >= 0; --k)
+    if (x[k]) return 32u * (uint32_t)k + 32u - (uint32_t)__builtin_clz(x[k]);
+  return 0;
+}
+
+// the split of Bob's chain: s1 <= q^3 < 2^768 and e < 2^256 ride the tail
+constexpr uint32_t kBobSplit = 768, kS1Limbs = 24, kELimbs = 8, kEBits = 256;
+// elements per simultaneous inversion (one serial chain of ~3 products each per group)
+constexpr uint32_t kInvChunk = 32;
+
+// the tail's descriptor block of J's instances: rows of `base` (stride bl limbs)
+// and `exp` (el limbs) by output row; the pads (row >= count) run exponent 0
+void tail_desc(const ModexpJob& J, uint32_t count, uint64_t base, uint32_t bl, uint64_t exp, uint32_t el,
+               std::vector<uint8_t>& d) {
+  const size_t n = J.size();
+  d.assign(n * kTailDescBytes, 0);
+  auto* bp = reinterpret_cast<uint64_t*>(d.data());
+  auto* ep = reinterpret_cast<uint64_t*>(d.data() + n * 8);
+  auto* ln = reinterpret_cast<uint32_t*>(d.data() + n * 16);
+  for (size_t k = 0; k < n; ++k) {
+    const uint32_t r = J.out_idx[k];
+    const uint32_t src = r < count ? r : 0u;
+    bp[k] = base + (size_t)src * bl * 4;
+    ep[k] = exp + (size_t)src * el * 4;
+    ln[k] = r < count ? el : 0u;
+  }
+}
+
+// instances in key order, cut into groups of at most kInvChunk of one key
+void inverse_groups(const uint32_t* key, uint32_t reps, uint32_t count, uint32_t n_keys, std::vector<uint32_t>& order,
+                    std::vector<uint32_t>& gstart) {
+  std::vector<std::vector<uint32_t>> by(n_keys);
+  for (uint32_t r = 0; r < reps; ++r)
+    for (uint32_t p = 0; p < count; ++p) by[key[p]].push_back(r * count + p);
+  order.clear();
+  gstart.assign(1, 0u);
+  for (const auto& v : by)
+    for (size_t s = 0; s < v.size(); s += kInvChunk) {
+      const size_t e = std::min(v.size(), s + kInvChunk);
+      order.insert(order.end(), v.begin() + s, v.begin() + e);
+      gstart.push_back((uint32_t)order.size());
+    }
+}
+
+// lanes per chain of the split launch: a forced context setting (tests, tuning)
+// where the tail has that shape, else by batch size
+int split_group(Ctx* c, const char* who, uint32_t count, bool wide_ok, uint32_t* group) {
+  const uint32_t f = c->modexp_group;
+  if (c->ct) {
+    c->fail("%s: public exponents only (constant-time context)", who);
+    return FSDKR_E_ARG;
+  }
+  if (f == 0) *group = keyed_lanes(count);   // as the keyed 4096-bit launches pick their lanes
+  else if (f == 4 || f == 8 || f == 16 || (wide_ok && f == kWideGroup)) *group = f;
+  else {
+    c->fail("%s: the split chains run at 4, 8, 16%s lanes (forced %u)", who, wide_ok ? " or 32" : "", f);
+    return FSDKR_E_ARG;
+  }
+  return FSDKR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fsdkr_modexp_joint3_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* base, const uint32_t* base2,
+                              const uint32_t* exp2, uint32_t exp2_limbs, const uint32_t* base3, const uint32_t* exp3,
+                              const uint32_t* mod_idx, const uint32_t* mods, const uint32_t* mod_exp,
+                              uint32_t exp_limbs, uint32_t n_mod, uint32_t* out) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return FSDKR_E_ARG;
+  if (count == 0) return FSDKR_OK;
+  const char* who = "fsdkr_modexp_joint3_batch";
+  constexpr uint32_t K = 128;
+  if (!base || !base2 || !exp2 || !mod_idx || !mods || !mod_exp || !out || !n_mod || !exp_limbs || !exp2_limbs ||
+      exp2_limbs > kS1Limbs || (base3 == nullptr) != (exp3 == nullptr)) {
+    c->fail("%s: bad argument", who);
+    return FSDKR_E_ARG;
+  }
+  uint32_t ebits = 1;
+  for (uint32_t m = 0; m < n_mod; ++m) {
+    if ((mods[(size_t)m * K] & 1u) == 0) {
+      c->fail("%s: modulus %u is even", who, m);
+      return FSDKR_E_ARG;
+    }
+    ebits = std::max(ebits, bit_len(mod_exp + (size_t)m * exp_limbs, exp_limbs));
+  }
+  for (uint32_t i = 0; i < count; ++i)
+    if (mod_idx[i] >= n_mod) {
+      c->fail("%s: mod_idx[%u] out of range", who, i);
+      return FSDKR_E_ARG;
+    }
+  uint32_t group = 16;
+  int rc;
+  if ((rc = split_group(c, who, count, true, &group))) return rc;
+  const uint32_t per_wave = 64 / group;
+  const size_t cap = (size_t)count + (size_t)n_mod * per_wave;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = al256(off + (bytes ? bytes : 1)); return o; };
+  const size_t o_b = take((size_t)count * K * 4), o_b2 = take((size_t)count * K * 4),
+               o_e2 = take((size_t)count * exp2_limbs * 4), o_b3 = take((size_t)count * K * 4),
+               o_e3 = take((size_t)count * kELimbs * 4), o_m = take((size_t)n_mod * K * 4),
+               o_me = take((size_t)n_mod * exp_limbs * 4), o_out = take(((size_t)count + 1) * K * 4),
+               o_desc = take(cap * 36), o_d2 = take(cap * kTailDescBytes), o_d3 = take(cap * kTailDescBytes);
+  uint8_t* dev = (uint8_t*)c->buf("mxj3", off);
+  if (!dev) {
+    c->fail("%s: device allocation failed", who);
+    return FSDKR_E_OOM;
+  }
+  auto DI = [&](size_t o) { return (uint64_t)(uintptr_t)(dev + o); };
+  ModexpJob J;
+  J.k32 = K;
+  for (uint32_t i = 0; i < count; ++i)
+    J.add(DI(o_b + (size_t)i * K * 4), K, DI(o_me + (size_t)mod_idx[i] * exp_limbs * 4), exp_limbs, ebits, mod_idx[i]);
+  if (!group_by_exponent(J, per_wave, count)) {
+    c->fail("%s: instances not wave-uniform", who);
+    return FSDKR_E_ARG;
+  }
+  std::vector<uint8_t> desc, d2, d3;
+  J.pack(desc);
+  tail_desc(J, count, DI(o_b2), K, DI(o_e2), exp2_limbs, d2);
+  if (base3) tail_desc(J, count, DI(o_b3), K, DI(o_e3), kELimbs, d3);
+  auto up = [&](size_t o, const void* src, size_t bytes) {
+    return c->hip_check(hipMemcpyAsync(dev + o, src, bytes, hipMemcpyHostToDevice, c->stream), "H2D joint3");
+  };
+  if ((rc = up(o_b, base, (size_t)count * K * 4)) || (rc = up(o_b2, base2, (size_t)count * K * 4)) ||
+      (rc = up(o_e2, exp2, (size_t)count * exp2_limbs * 4)) || (rc = up(o_m, mods, (size_t)n_mod * K * 4)) ||
+      (rc = up(o_me, mod_exp, (size_t)n_mod * exp_limbs * 4)) || (rc = up(o_desc, desc.data(), desc.size())) ||
+      (rc = up(o_d2, d2.data(), d2.size())))
+    return rc;
+  if (base3 && ((rc = up(o_b3, base3, (size_t)count * K * 4)) || (rc = up(o_e3, exp3, (size_t)count * kELimbs * 4)) ||
+                (rc = up(o_d3, d3.data(), d3.size()))))
+    return rc;
+  uint32_t* cons = nullptr;
+  if ((rc = setup_moduli(c, K, reinterpret_cast<const uint32_t*>(dev + o_m), n_mod, &cons,
+                         group == kWideGroup ? "joint3_w" : "joint3", group == kWideGroup ? kWideGroup : 0u)))
+    return rc;
+  const uint32_t flags = ga_desc_flags(true, group);
+  SplitArgs head;
+  head.lo_bit = kBobSplit;
+  SplitArgs tail = head;
+  tail.tail = true;
+  tail.d_desc2 = dev + o_d2;
+  if (base3) {
+    tail.d_desc3 = dev + o_d3;
+    tail.exp3_bits = kEBits;
+  }
+  const size_t n = J.size();
+  uint32_t* d_out = reinterpret_cast<uint32_t*>(dev + o_out);
+  if ((rc = launch_modexp_desc(c, K, (uint32_t)n, ebits, dev + o_desc, cons, d_out, c->stream, "mxt_joint3", 0, group,
+                               flags, &head)) ||
+      (rc = launch_modexp_desc(c, K, (uint32_t)n, ebits, dev + o_desc, cons, d_out, c->stream, "mxt_joint3", 0, group,
+                               flags, &tail)))
+    return rc;
+  if ((rc = c->hip_check(hipMemcpyAsync(out, d_out, (size_t)count * K * 4, hipMemcpyDeviceToHost, c->stream), "D2H")))
+    return rc;
+  return c->sync();
+}
+
+static int bob_verify_impl(Ctx* c, const char* who, const fsdkr_bob_batch* b, uint8_t* verdict, bool fused) {
+  if (!b) {
+    c->fail("%s: null batch", who);
+    return FSDKR_E_ARG;
+  }
+  const uint32_t count = b->count, nk = b->n_keys, nl = b->nl, nn = 2 * b->nl;
+  if (count == 0) return FSDKR_OK;
+  if (!verdict || !nk || !b->N || !b->Ntilde || !b->h1 || !b->h2 || !b->key_idx || !b->a_enc || !b->mta || !b->z ||
+      !b->t || !b->s || !b->e || !b->s1 || !b->s2 || !b->t1 || !b->t2 || (b->X == nullptr) != (b->u == nullptr) ||
+      !b->el || !b->s1l || !b->s2l || !b->t1l || !b->t2l || b->el > 64 || b->s1l > 64) {
+    c->fail("%s: bad argument", who);
+    return FSDKR_E_ARG;
+  }
+  if (nl != 64) {
+    c->fail("%s: unsupported modulus width %u limbs", who, nl);
+    return FSDKR_E_UNSUPPORTED;
+  }
+  const bool ext = b->X != nullptr;
+  for (uint32_t k = 0; k < nk; ++k) {
+    const uint32_t *N = b->N + (size_t)k * nl, *Nt = b->Ntilde + (size_t)k * nl;
+    if (!(N[0] & 1u) || !(Nt[0] & 1u) || bit_len(N, nl) < 2 || bit_len(Nt, nl) < 2) {
+      c->fail("%s: key %u: N and Ntilde must be odd and above 1", who, k);
+      return FSDKR_E_ARG;
+    }
+  }
+  for (uint32_t p = 0; p < count; ++p)
+    if (b->key_idx[p] >= nk) {
+      c->fail("%s: key_idx[%u] out of range", who, p);
+      return FSDKR_E_ARG;
+    }
+  uint32_t group = 16;
+  int rc;
+  if ((rc = split_group(c, who, count, false, &group))) return rc;
+  const uint32_t* key = b->key_idx;
+
+  // ---- host pre-pass -------------------------------------------------------
+  static const uint32_t kQ[8] = {0xD0364141u, 0xBFD25E8Cu, 0xAF48A03Bu, 0xBAAEDCE6u,
+                                 0xFFFFFFFEu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+  const hbn::Limbs q = hbn::from(kQ, 8), q3 = hbn::mul(hbn::mul(q, q), q);
+  std::vector<uint8_t> pre(count, 1), inf(count, 0);
+  std::vector<uint32_t> s1a((size_t)count * kS1Limbs, 0u), ea((size_t)count * kELimbs, 0u);
+  for (uint32_t p = 0; p < count; ++p) {
+    const uint32_t* s1 = b->s1 + (size_t)p * b->s1l;
+    if (hbn::cmp_raw(s1, b->s1l, q3.data(), q3.size()) > 0) pre[p] = 0;   // :374 (s1 == q^3 passes)
+    else memcpy(&s1a[(size_t)p * kS1Limbs], s1, std::min(b->s1l, kS1Limbs) * 4);
+    const uint32_t* e = b->e + (size_t)p * b->el;
+    bool wide = false;
+    for (uint32_t k = kELimbs; k < b->el; ++k) wide = wide || e[k] != 0;
+    if (!wide) memcpy(&ea[(size_t)p * kELimbs], e, std::min(b->el, kELimbs) * 4);
+    // a challenge of 256 bits or more never equals the hash; e = 0 only if the hash is 0
+    if (wide || hbn::is_zero_raw(&ea[(size_t)p * kELimbs], kELimbs)) pre[p] = 0;
+    if (ext) inf[p] = hbn::is_zero_raw(b->X + (size_t)p * 16, 16) || hbn::is_zero_raw(b->u + (size_t)p * 16, 16);
+  }
+  std::vector<uint32_t> NN((size_t)nk * nn), h1r((size_t)nk * nl), h2r((size_t)nk * nl);
+  uint32_t nbits = 1;
+  for (uint32_t k = 0; k < nk; ++k) {
+    const hbn::Limbs N = hbn::from(b->N + (size_t)k * nl, nl), Nt = hbn::from(b->Ntilde + (size_t)k * nl, nl);
+    hbn::store(hbn::mul(N, N), &NN[(size_t)k * nn], nn);
+    hbn::store(hbn::mod(hbn::from(b->h1 + (size_t)k * nl, nl), Nt), &h1r[(size_t)k * nl], nl);
+    hbn::store(hbn::mod(hbn::from(b->h2 + (size_t)k * nl, nl), Nt), &h2r[(size_t)k * nl], nl);
+    nbits = std::max(nbits, bit_len(b->N + (size_t)k * nl, nl));
+  }
+  // rows at or above their modulus are reduced for the arithmetic (a copy, made only then)
+  auto reduced = [&](const uint32_t* src, uint32_t L, const uint32_t* mods, uint32_t ML,
+                     std::vector<uint32_t>& store) -> const uint32_t* {
+    for (uint32_t p = 0; p < count; ++p) {
+      const uint32_t* m = mods + (size_t)key[p] * ML;
+      if (hbn::cmp_raw(src + (size_t)p * L, L, m, ML) < 0) continue;
+      if (store.empty()) store.assign(src, src + (size_t)count * L);
+      hbn::store(hbn::mod(hbn::from(src + (size_t)p * L, L), hbn::from(m, ML)), &store[(size_t)p * L], L);
+    }
+    return store.empty() ? src : store.data();
+  };
+  std::vector<uint32_t> v_a, v_m, v_z, v_t, v_s;
+  const uint32_t* a_red = reduced(b->a_enc, nn, NN.data(), nn, v_a);
+  const uint32_t* m_red = reduced(b->mta, nn, NN.data(), nn, v_m);
+  const uint32_t* z_red = reduced(b->z, nl, b->Ntilde, nl, v_z);
+  const uint32_t* t_red = reduced(b->t, nl, b->Ntilde, nl, v_t);
+  const uint32_t* s_red = reduced(b->s, nl, NN.data(), nn, v_s);
+  // 1 + t1 N = 1 + (t1 mod N) N  (mod N^2): the honest t1 = e beta' + gamma is wider than N
+  std::vector<uint32_t> t1r((size_t)count * nl, 0u);
+  for (uint32_t p = 0; p < count; ++p) {
+    const uint32_t* t1 = b->t1 + (size_t)p * b->t1l;
+    const uint32_t* N = b->N + (size_t)key[p] * nl;
+    if (hbn::cmp_raw(t1, b->t1l, N, nl) < 0) memcpy(&t1r[(size_t)p * nl], t1, std::min(b->t1l, nl) * 4);
+    else hbn::store(hbn::mod(hbn::from(t1, b->t1l), hbn::from(N, nl)), &t1r[(size_t)p * nl], nl);
+  }
+  uint32_t s1bits = 1, s2bits = 1, t1bits = 1, t2bits = 1;
+  for (uint32_t p = 0; p < count; ++p) {
+    s1bits = std::max(s1bits, bit_len(&s1a[(size_t)p * kS1Limbs], kS1Limbs));
+    s2bits = std::max(s2bits, bit_len(b->s2 + (size_t)p * b->s2l, b->s2l));
+    t1bits = std::max(t1bits, bit_len(b->t1 + (size_t)p * b->t1l, b->t1l));
+    t2bits = std::max(t2bits, bit_len(b->t2 + (size_t)p * b->t2l, b->t2l));
+  }
+
+  // ---- device image --------------------------------------------------------
+  const size_t C = count, rl = (size_t)nl * 4, rn = (size_t)nn * 4;
+  const uint32_t per_wave = 64 / group;
+  const size_t cap = C + (size_t)nk * per_wave;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = al256(off + (bytes ? bytes : 1)); return o; };
+  const size_t o_N = take(nk * rl), o_Nt = take(nk * rl), o_NN = take(nk * rn), o_h1 = take(nk * rl), o_h2 = take(nk * rl);
+  const size_t o_a = take(C * rn), o_m = take(C * rn), o_z = take(C * rl), o_t = take(C * rl), o_s = take(C * rl);
+  const size_t o_ar = v_a.empty() ? o_a : take(C * rn), o_mr = v_m.empty() ? o_m : take(C * rn);
+  const size_t o_zt = take(2 * C * rl);   // z | t reduced (the z^e | t^e bases)
+  const size_t o_e = take(C * b->el * 4), o_ea = take(C * kELimbs * 4), o_s1 = take(C * kS1Limbs * 4);
+  const size_t o_s1raw = take(C * b->s1l * 4), o_s2 = take(C * b->s2l * 4), o_t1 = take(C * b->t1l * 4);
+  const size_t o_t1r = take(C * rl), o_t2 = take(C * b->t2l * 4), o_X = take(ext ? C * 64 : 0), o_u = take(ext ? C * 64 : 0);
+  const size_t o_one = take(rn), o_pre = take(C), o_ec = take(C);
+  // descriptors
+  const size_t o_gdesc = take(cap * 36), o_gd2 = take(cap * kTailDescBytes), o_gd3 = take(cap * kTailDescBytes);
+  const size_t o_zdesc = take(2 * C * 32), o_udesc = take(fused ? 0 : 2 * C * 32 + 512);
+  const size_t o_iy = take(3 * C * 8), o_im = take(3 * C * 8), o_iord = take(3 * C * 4), o_igs = take((3 * C + 2 * nk + 2) * 4);
+  const size_t o_bs = take(C * 8), o_bn = take(C * 8);
+  const size_t o_p3 = take(3 * C * sizeof(Prod3Operand)), o_p3m = take(3 * C * 4), o_hn = take(C * 8);
+  // results
+  const size_t o_minv = take(C * rn), o_um = take(C * 4), o_zte = take(2 * C * rl), o_ztinv = take(2 * C * rl);
+  const size_t o_uzt = take(2 * C * 4), o_fb = take(4 * C * rl), o_binom = take(C * rn), o_ga = take((C + 1) * rn);
+  const size_t o_un = take(fused ? 0 : 3 * C * rn);   // unfused: a_enc^s1 | mta^e | (mta^e)^-1
+  const size_t o_v0 = take(fused ? 0 : C * rn), o_p3u = take(fused ? 0 : C * sizeof(Prod3Operand));
+  const size_t o_zw = take(2 * C * rl), o_v = take(C * rn);
+  const size_t o_iscr = take(2 * C * 144 * 4);
+  uint8_t* dev = (uint8_t*)c->buf("bob_io", off);
+  if (!dev) {
+    c->fail("%s: device allocation failed (%zu bytes)", who, off);
+    return FSDKR_E_OOM;
+  }
+  auto DA = [&](size_t o) { return (uint64_t)(uintptr_t)(dev + o); };
+  auto PU = [&](size_t o) { return reinterpret_cast<uint32_t*>(dev + o); };
+  hipStream_t st = c->stream;
+  auto up = [&](size_t o, const void* src, size_t bytes) {
+    return bytes ? c->hip_check(hipMemcpyAsync(dev + o, src, bytes, hipMemcpyHostToDevice, st), "H2D bob") : (int)FSDKR_OK;
+  };
+  std::vector<uint32_t> one(nn, 0u);
+  one[0] = 1;
+
+  // GA: s^N mod N^2, regrouped so every wave shares its exponent N
+  ModexpJob J;
+  J.k32 = nn;
+  for (uint32_t p = 0; p < count; ++p)
+    J.add(DA(o_s + p * rl), nl, DA(o_N + key[p] * rl), nl, bit_len(b->N + (size_t)key[p] * nl, nl), key[p]);
+  if (!group_by_exponent(J, per_wave, count)) {
+    c->fail("%s: instances not wave-uniform", who);
+    return FSDKR_E_ARG;
+  }
+  std::vector<uint8_t> gdesc, gd2, gd3;
+  J.pack(gdesc);
+  if (fused) {
+    tail_desc(J, count, DA(o_ar), nn, DA(o_s1), kS1Limbs, gd2);
+    tail_desc(J, count, DA(o_minv), nn, DA(o_ea), kELimbs, gd3);
+  }
+  // z^e | t^e mod N~
+  ModexpJob Jz;
+  Jz.k32 = nl;
+  for (uint32_t i = 0; i < 2 * count; ++i)
+    Jz.add(DA(o_zt + i * rl), nl, DA(o_ea + (size_t)(i % count) * kELimbs * 4), kELimbs, kEBits, key[i % count]);
+  std::vector<uint8_t> zdesc;
+  Jz.pack(zdesc);
+  // unfused: a_enc^s1 | mta^e mod N^2 as chains of their own
+  ModexpJob Ju, Jm;
+  std::vector<uint8_t> udesc;
+  if (!fused) {
+    Ju.k32 = Jm.k32 = nn;
+    for (uint32_t p = 0; p < count; ++p) {
+      Ju.add(DA(o_ar + p * rn), nn, DA(o_s1 + (size_t)p * kS1Limbs * 4), kS1Limbs, std::max(s1bits, 1u), key[p]);
+      Jm.add(DA(o_mr + p * rn), nn, DA(o_ea + (size_t)p * kELimbs * 4), kELimbs, kEBits, key[p]);
+    }
+    Ju.pack(udesc);
+    udesc.resize(al256(udesc.size()));
+    Jm.pack(udesc);
+  }
+  // inverses: mta (fused; unfused mta^e) mod N^2, then z^e | t^e mod N~
+  std::vector<uint64_t> iy(3 * C), im(3 * C);
+  std::vector<uint32_t> ord_nn, gs_nn, ord_nl, gs_nl;
+  inverse_groups(key, 1, count, nk, ord_nn, gs_nn);
+  inverse_groups(key, 2, count, nk, ord_nl, gs_nl);
+  for (uint32_t p = 0; p < count; ++p) {
+    iy[p] = fused ? DA(o_mr + p * rn) : DA(o_un + (C + p) * rn);
+    im[p] = DA(o_NN + key[p] * rn);
+  }
+  for (uint32_t i = 0; i < 2 * count; ++i) {
+    iy[C + i] = DA(o_zte + i * rl);
+    im[C + i] = DA(o_Nt + key[i % count] * rl);
+  }
+  std::vector<uint32_t> iord(ord_nn);
+  iord.insert(iord.end(), ord_nl.begin(), ord_nl.end());
+  std::vector<uint32_t> igs(gs_nn);
+  const size_t igs_nl = igs.size();
+  igs.insert(igs.end(), gs_nl.begin(), gs_nl.end());
+  // fixed-base job: h1^s1 | h2^s2 | h1^t1 | h2^t2, bases [h1_k | h2_k]
+  FbJob fb;
+  fb.k32 = nl;
+  for (uint32_t k = 0; k < nk; ++k) fb.add_base(DA(o_h1 + k * rl), nl, k);
+  for (uint32_t k = 0; k < nk; ++k) fb.add_base(DA(o_h2 + k * rl), nl, k);
+  const uint32_t h1bits = std::max(s1bits, t1bits), h2bits = std::max(s2bits, t2bits);
+  for (uint32_t p = 0; p < count; ++p) {
+    fb.add(key[p], DA(o_s1 + (size_t)p * kS1Limbs * 4), kS1Limbs, h1bits, DA(o_fb + (0 * C + p) * rl));
+    fb.add(key[p], DA(o_t1 + (size_t)p * b->t1l * 4), b->t1l, h1bits, DA(o_fb + (2 * C + p) * rl));
+  }
+  for (uint32_t p = 0; p < count; ++p) {
+    fb.add(nk + key[p], DA(o_s2 + (size_t)p * b->s2l * 4), b->s2l, h2bits, DA(o_fb + (1 * C + p) * rl));
+    fb.add(nk + key[p], DA(o_t2 + (size_t)p * b->t2l * 4), b->t2l, h2bits, DA(o_fb + (3 * C + p) * rl));
+  }
+  fb.finalize();
+  // binom, products, hash
+  std::vector<uint64_t> bs(C), bn(C), hn(C);
+  std::vector<Prod3Operand> p3(3 * C);
+  std::vector<uint32_t> p3m(3 * C);
+  for (uint32_t p = 0; p < count; ++p) {
+    bs[p] = DA(o_t1r + p * rl);
+    bn[p] = hn[p] = DA(o_N + key[p] * rl);
+    // z' = h1^s1 h2^s2 (z^e)^-1, w = h1^t1 h2^t2 (t^e)^-1 mod N~
+    p3[p] = Prod3Operand{DA(o_fb + (0 * C + p) * rl), DA(o_fb + (1 * C + p) * rl), DA(o_ztinv + p * rl), nl, nl, nl, 0};
+    p3[C + p] = Prod3Operand{DA(o_fb + (2 * C + p) * rl), DA(o_fb + (3 * C + p) * rl), DA(o_ztinv + (C + p) * rl),
+                             nl, nl, nl, 0};
+    // v = (chain) (1 + t1 N) mod N^2
+    p3[2 * C + p] = Prod3Operand{fused ? DA(o_ga + p * rn) : DA(o_v0 + p * rn), DA(o_binom + p * rn), DA(o_one), nn, nn, nn, 0};
+    p3m[p] = p3m[C + p] = p3m[2 * C + p] = key[p];
+  }
+  std::vector<Prod3Operand> p3u;   // unfused: s^N a_enc^s1 (mta^e)^-1
+  if (!fused) {
+    p3u.resize(C);
+    for (uint32_t p = 0; p < count; ++p)
+      p3u[p] = Prod3Operand{DA(o_ga + p * rn), DA(o_un + p * rn), DA(o_un + (2 * C + p) * rn), nn, nn, nn, 0};
+  }
+  std::vector<uint32_t> zt((size_t)2 * count * nl);
+  memcpy(zt.data(), z_red, C * rl);
+  memcpy(zt.data() + (size_t)count * nl, t_red, C * rl);
+
+  if ((rc = up(o_N, b->N, nk * rl)) || (rc = up(o_Nt, b->Ntilde, nk * rl)) || (rc = up(o_NN, NN.data(), nk * rn)) ||
+      (rc = up(o_h1, h1r.data(), nk * rl)) || (rc = up(o_h2, h2r.data(), nk * rl)) || (rc = up(o_a, b->a_enc, C * rn)) ||
+      (rc = up(o_m, b->mta, C * rn)) || (rc = up(o_z, b->z, C * rl)) || (rc = up(o_t, b->t, C * rl)) ||
+      (rc = up(o_s, s_red, C * rl)) || (!v_a.empty() && (rc = up(o_ar, a_red, C * rn))) ||
+      (!v_m.empty() && (rc = up(o_mr, m_red, C * rn))) || (rc = up(o_zt, zt.data(), 2 * C * rl)) ||
+      (rc = up(o_e, b->e, C * b->el * 4)) || (rc = up(o_ea, ea.data(), C * kELimbs * 4)) ||
+      (rc = up(o_s1, s1a.data(), C * kS1Limbs * 4)) || (rc = up(o_s1raw, b->s1, C * b->s1l * 4)) ||
+      (rc = up(o_s2, b->s2, C * b->s2l * 4)) || (rc = up(o_t1, b->t1, C * b->t1l * 4)) ||
+      (rc = up(o_t1r, t1r.data(), C * rl)) || (rc = up(o_t2, b->t2, C * b->t2l * 4)) ||
+      (ext && ((rc = up(o_X, b->X, C * 64)) || (rc = up(o_u, b->u, C * 64)))) || (rc = up(o_one, one.data(), rn)) ||
+      (rc = up(o_pre, pre.data(), C)) || (rc = up(o_gdesc, gdesc.data(), gdesc.size())) ||
+      (fused && ((rc = up(o_gd2, gd2.data(), gd2.size())) || (rc = up(o_gd3, gd3.data(), gd3.size())))) ||
+      (rc = up(o_zdesc, zdesc.data(), zdesc.size())) || (!fused && (rc = up(o_udesc, udesc.data(), udesc.size()))) ||
+      (rc = up(o_iy, iy.data(), iy.size() * 8)) || (rc = up(o_im, im.data(), im.size() * 8)) ||
+      (rc = up(o_iord, iord.data(), iord.size() * 4)) || (rc = up(o_igs, igs.data(), igs.size() * 4)) ||
+      (rc = up(o_bs, bs.data(), C * 8)) || (rc = up(o_bn, bn.data(), C * 8)) || (rc = up(o_hn, hn.data(), C * 8)) ||
+      (rc = up(o_p3, p3.data(), p3.size() * sizeof(Prod3Operand))) || (rc = up(o_p3m, p3m.data(), p3m.size() * 4)) ||
+      (!fused && (rc = up(o_p3u, p3u.data(), p3u.size() * sizeof(Prod3Operand)))))
+    return rc;
+  if (ext && (rc = c->hip_check(hipMemsetAsync(dev + o_ec, 0, C, st), "memset ec"))) return rc;
+
+  // ---- kernels -------------------------------------------------------------
+  uint32_t *cons_nl = nullptr, *cons_nn = nullptr;
+  if ((rc = setup_moduli(c, nl, PU(o_Nt), nk, &cons_nl, "bob_nl")) || (rc = setup_moduli(c, nn, PU(o_NN), nk, &cons_nn, "bob_nn")))
+    return rc;
+  uint32_t* iscr = PU(o_iscr);   // [C][144] for the N^2 inverse, then [2C][72] for the N~ ones
+  hipEvent_t ready = nullptr, side_done = nullptr;
+  auto drop = [&](int r) {
+    if (ready) (void)hipEventDestroy(ready);
+    if (side_done) (void)hipEventDestroy(side_done);
+    ready = side_done = nullptr;
+    return r;
+  };
+  if ((rc = c->hip_check(hipEventCreateWithFlags(&ready, hipEventDisableTiming), "event")) ||
+      (rc = c->hip_check(hipEventCreateWithFlags(&side_done, hipEventDisableTiming), "event")) ||
+      (rc = c->hip_check(hipEventRecord(ready, st), "event record")))   // uploads and constants are in
+    return drop(rc);
+  auto inverse_nn = [&](uint32_t* out, uint32_t* unit) {
+    BatchInverseArgs a{(const uint64_t*)(dev + o_iy), (const uint64_t*)(dev + o_im), PU(o_iord), PU(o_igs), out, unit,
+                       iscr, (uint32_t)gs_nn.size() - 1};
+    c->mark("inverse", true);
+    const int r = c->hip_check(launch_inverse_batch(nn, a, st), "inverse nn");
+    c->mark("inverse", false);
+    return r;
+  };
+  const uint32_t flags = ga_desc_flags(true, group);
+  const uint32_t gn = (uint32_t)J.size();
+  SplitArgs head;
+  head.lo_bit = kBobSplit;
+  if (fused) {
+    // mta^-1 (and mta's unit flag), then s^N a_enc^s1 (mta^-1)^e in one chain
+    if ((rc = inverse_nn(PU(o_minv), PU(o_um)))) return drop(rc);
+    SplitArgs tail = head;
+    tail.tail = true;
+    tail.d_desc2 = dev + o_gd2;
+    tail.d_desc3 = dev + o_gd3;
+    tail.exp3_bits = kEBits;
+    if ((rc = launch_modexp_desc(c, nn, gn, nbits, dev + o_gdesc, cons_nn, PU(o_ga), st, "mxt_bob", 0, group, flags, &head)) ||
+        (rc = launch_modexp_desc(c, nn, gn, nbits, dev + o_gdesc, cons_nn, PU(o_ga), st, "mxt_bob", 0, group, flags, &tail)))
+      return drop(rc);
+  } else {
+    // s^N (keyed sliding windows), a_enc^s1, mta^e and its inverse, then their product
+    if ((rc = launch_modexp_desc(c, nn, gn, nbits, dev + o_gdesc, cons_nn, PU(o_ga), st, "mxt_bob", 0, group, flags)) ||
+        (rc = launch_modexp_desc(c, nn, count, Ju.exp_bits, dev + o_udesc, cons_nn, PU(o_un), st, "mxt_bob_u")) ||
+        (rc = launch_modexp_desc(c, nn, count, kEBits, dev + o_udesc + al256(Ju.desc_bytes()), cons_nn,
+                                 PU(o_un) + C * nn, st, "mxt_bob_m")) ||
+        (rc = inverse_nn(PU(o_un) + 2 * C * nn, PU(o_um))))
+      return drop(rc);
+    Prod3Args pu{(const Prod3Operand*)(dev + o_p3u), PU(o_p3m), cons_nn, PU(o_v0), count};
+    if ((rc = c->hip_check(launch_prod3(nn, pu, st), "prod3 nn"))) return drop(rc);
+  }
+  // the N~ side -- z^e | t^e, their inverses, the fixed-base job -- on a side stream
+  // beside the N^2 chains enqueued above (at 16 lanes they leave SIMD slots free)
+  {
+    hipStream_t ss = c->side_stream(1);
+    (void)hipStreamWaitEvent(ss, ready, 0);
+    StreamScope scope(c, ss);
+    if ((rc = launch_modexp_desc(c, nl, 2 * count, kEBits, dev + o_zdesc, cons_nl, PU(o_zte), ss, "mxt_bob_z")))
+      return drop(rc);
+    BatchInverseArgs a{(const uint64_t*)(dev + o_iy) + C, (const uint64_t*)(dev + o_im) + C, PU(o_iord) + C,
+                       PU(o_igs) + igs_nl, PU(o_ztinv), PU(o_uzt), iscr + C * 144, (uint32_t)gs_nl.size() - 1};
+    c->mark("inverse", true);
+    rc = c->hip_check(launch_inverse_batch(nl, a, ss), "inverse nl");
+    c->mark("inverse", false);
+    if (rc || (rc = fb_run(c, fb, cons_nl, "bob")) ||
+        (rc = c->hip_check(hipEventRecord(side_done, ss), "event record")))
+      return drop(rc);
+  }
+  (void)hipStreamWaitEvent(st, side_done, 0);
+  drop(0);
+  {
+    BinomArgs a{(const uint64_t*)(dev + o_bs), (const uint64_t*)(dev + o_bn), nl, nl, nn, PU(o_binom), count};
+    if ((rc = c->hip_check(launch_binom(a, st), "binom"))) return rc;
+    Prod3Args pa{(const Prod3Operand*)(dev + o_p3), PU(o_p3m), cons_nl, PU(o_zw), 2 * count};
+    if ((rc = c->hip_check(launch_prod3(nl, pa, st), "prod3 nl"))) return rc;
+    Prod3Args pb{(const Prod3Operand*)(dev + o_p3) + 2 * C, PU(o_p3m) + 2 * C, cons_nn, PU(o_v), count};
+    if ((rc = c->hip_check(launch_prod3(nn, pb, st), "prod3 nn"))) return rc;
+  }
+  {
+    BobHashArgs h{(const uint64_t*)(dev + o_hn), PU(o_a), PU(o_m), PU(o_z), PU(o_t), PU(o_zw), PU(o_zw) + C * nl,
+                  PU(o_v), PU(o_e), ext ? PU(o_X) : nullptr, ext ? PU(o_u) : nullptr, nl, nn, nl, b->el,
+                  dev + o_pre, count};
+    c->mark("bob_hash", true);
+    rc = c->hip_check(launch_bob_hash(h, st), "bob_hash");
+    c->mark("bob_hash", false);
+    if (rc) return rc;
+  }
+  if (ext) {   // G s1 == X e + u  (:550-559)
+    PdlU1Args u{PU(o_s1raw), PU(o_ea), PU(o_X), PU(o_u), b->s1l, dev + o_ec, count};
+    c->mark("ec", true);
+    rc = c->hip_check(launch_pdl_u1(u, st), "pdl_u1");
+    c->mark("ec", false);
+    if (rc) return rc;
+  }
+  std::vector<uint8_t> hv(count), ec(count, 1);
+  std::vector<uint32_t> um(count), uzt(2 * C);
+  if ((rc = c->hip_check(hipMemcpyAsync(hv.data(), dev + o_pre, C, hipMemcpyDeviceToHost, st), "D2H bob")) ||
+      (rc = c->hip_check(hipMemcpyAsync(um.data(), dev + o_um, C * 4, hipMemcpyDeviceToHost, st), "D2H bob")) ||
+      (rc = c->hip_check(hipMemcpyAsync(uzt.data(), dev + o_uzt, 2 * C * 4, hipMemcpyDeviceToHost, st), "D2H bob")) ||
+      (ext && (rc = c->hip_check(hipMemcpyAsync(ec.data(), dev + o_ec, C, hipMemcpyDeviceToHost, st), "D2H bob"))))
+    return rc;
+  if ((rc = c->sync())) return rc;
+  for (uint32_t p = 0; p < count; ++p) {
+    // s1 bound, then the three inverses (:374-406); only then the coordinates' unwrap (:428-431)
+    const bool gate = pre[p] && uzt[p] && um[p] && uzt[C + p];
+    verdict[p] = !gate ? 0 : inf[p] ? 2 : (hv[p] && (ec[p] & 1u)) ? 1 : 0;
+  }
+  return FSDKR_OK;
+}
+
+int fsdkr_bob_verify(fsdkr_ctx* ctx, const fsdkr_bob_batch* batch, uint8_t* verdict) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return FSDKR_E_ARG;
+  return bob_verify_impl(c, "fsdkr_bob_verify", batch, verdict, true);
+}
+
+int fsdkr_bob_verify_unfused(fsdkr_ctx* ctx, const fsdkr_bob_batch* batch, uint8_t* verdict) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return FSDKR_E_ARG;
+  return bob_verify_impl(c, "fsdkr_bob_verify_unfused", batch, verdict, false);
+}
+
+}  // extern "C"

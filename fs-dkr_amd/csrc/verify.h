@@ -36,6 +36,21 @@ struct AliceHashArgs {      // H(N, N+1, c, z, u, w) == e
   uint32_t* state;          // [count][32] SHA-256 state after H(N, N+1, c, z) (alice_prefix), or null
 };
 
+// Bob's transcript (range_proofs.rs:413-441):
+// H(N, N+1, a_enc, mta, z, z', t, v, w [, X.x, X.y, u.x, u.y]) == e
+struct BobHashArgs {
+  const uint64_t* n_ptr;    // [count] verifier N (n_len limbs)
+  const uint32_t *a_enc, *mta;   // [count][c_len] as given (not reduced)
+  const uint32_t *z, *t;    // [count][z_len] as given
+  const uint32_t *zp, *w;   // [count][z_len] computed z', w
+  const uint32_t* v;        // [count][c_len] computed v
+  const uint32_t* e;        // [count][e_len]
+  const uint32_t *X, *u;    // [count][16] affine points (x | y), or both null: the plain proof
+  uint32_t n_len, c_len, z_len, e_len;
+  uint8_t* verdict;         // in: host pre-checks, out: AND hash equality
+  uint32_t count;
+};
+
 struct InverseArgs {
   const uint64_t* y_ptr;    // value to invert (reduced, K32 limbs)
   const uint64_t* m_ptr;    // odd modulus (K32 limbs)
@@ -149,6 +164,7 @@ hipError_t launch_binom(const BinomArgs& a, hipStream_t st);
 hipError_t launch_ped_hash(const PedHashArgs& a, hipStream_t st);
 hipError_t launch_alice_hash(const AliceHashArgs& a, hipStream_t st);
 hipError_t launch_alice_prefix(const AliceHashArgs& a, hipStream_t st);
+hipError_t launch_bob_hash(const BobHashArgs& a, hipStream_t st);
 hipError_t launch_inverse(uint32_t k32, const InverseArgs& a, hipStream_t st);
 // lane-cooperative Pornin inverse (inverse.hip): registers + DPP
 hipError_t launch_inverse_coop(uint32_t k32, const InverseArgs& a, hipStream_t st);

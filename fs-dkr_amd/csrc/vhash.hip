@@ -234,7 +234,58 @@ __global__ void alice_hash_kernel(const AliceHashArgs a) {
   a.verdict[p] = (a.verdict[p] && eq) ? 1 : 0;
 }
 
+// Bob's e' = H(N, N+1, a_enc, mta, z, z', t, v, w [, X.x, X.y, u.x, u.y]) == e
+// (range_proofs.rs:413-441; BobProofExt adds the four coordinates, :428-435).  The
+// inputs are hashed as given, z', v, w as computed.  An e wider than 256 bits
+// never matches.  One thread per proof, as alice_hash_kernel.
+__global__ void bob_hash_kernel(const BobHashArgs a) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= a.count) return;
+  __shared__ uint32_t sha_w[64 * 16];  // launch blocks are 64 threads
+  Sha256 h;
+  h.init(sha_w + threadIdx.x * 16);
+  const uint32_t* N = P32(a.n_ptr[p]);
+  h.bigint(N, a.n_len);
+  {
+    uint32_t np1[128];
+    uint64_t c = 1;
+    for (uint32_t k = 0; k < a.n_len; ++k) {
+      c += N[k];
+      np1[k] = (uint32_t)c;
+      c >>= 32;
+    }
+    if (c) np1[a.n_len] = 1;
+    h.bigint(np1, a.n_len + (c ? 1u : 0u));
+  }
+  h.bigint(a.a_enc + (size_t)p * a.c_len, a.c_len);
+  h.bigint(a.mta + (size_t)p * a.c_len, a.c_len);
+  h.bigint(a.z + (size_t)p * a.z_len, a.z_len);
+  h.bigint(a.zp + (size_t)p * a.z_len, a.z_len);
+  h.bigint(a.t + (size_t)p * a.z_len, a.z_len);
+  h.bigint(a.v + (size_t)p * a.c_len, a.c_len);
+  h.bigint(a.w + (size_t)p * a.z_len, a.z_len);
+  if (a.X) {
+    h.bigint(a.X + (size_t)p * 16, 8);
+    h.bigint(a.X + (size_t)p * 16 + 8, 8);
+    h.bigint(a.u + (size_t)p * 16, 8);
+    h.bigint(a.u + (size_t)p * 16 + 8, 8);
+  }
+  uint32_t d[8];
+  h.finish_le(d);
+  const uint32_t* e = a.e + (size_t)p * a.e_len;
+  bool eq = true;
+  for (uint32_t k = 0; k < a.e_len; ++k) eq = eq && (e[k] == (k < 8 ? d[k] : 0u));
+  for (uint32_t k = a.e_len; k < 8; ++k) eq = eq && (d[k] == 0u);
+  a.verdict[p] = (a.verdict[p] && eq) ? 1 : 0;
+}
+
 // ------------------------------------------------------------- launchers -------
+hipError_t launch_bob_hash(const BobHashArgs& a, hipStream_t st) {
+  if (!a.count) return hipSuccess;
+  if (a.n_len > 127u || (a.X == nullptr) != (a.u == nullptr)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(bob_hash_kernel, dim3(blocks_for(a.count, 64)), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
 hipError_t launch_binom(const BinomArgs& a, hipStream_t st) {
   if (!a.count) return hipSuccess;
   hipLaunchKernelGGL(binom_kernel, dim3(blocks_for(a.count, 128)), dim3(128), 0, st, a);

@@ -58,6 +58,13 @@ class VerdictsC(ctypes.Structure):
                [(f, ctypes.c_uint32) for f in ("cap_pairs", "cap_msgs", "cap_joins")]
 
 
+class BobBatchC(ctypes.Structure):
+    """struct fsdkr_bob_batch (include/fsdkr/fsdkr.h)."""
+    _fields_ = [(f, ctypes.c_uint32) for f in ("count", "n_keys", "nl", "el", "s1l", "s2l", "t1l", "t2l")] + \
+               [(f, u32p) for f in ("N", "Ntilde", "h1", "h2", "key_idx", "a_enc", "mta", "z", "t", "s", "e",
+                                    "s1", "s2", "t1", "t2", "X", "u")]
+
+
 class RecoverJobC(ctypes.Structure):
     _fields_ = [("nl", ctypes.c_uint32), ("t_vss", ctypes.c_uint32), ("t_key", ctypes.c_uint32),
                 ("n_new", ctypes.c_uint32), ("old_index", u32p), ("cts", u32p), ("p", u32p), ("q", u32p),
@@ -133,6 +140,13 @@ def lib():
     L.fsdkr_modexp_joint_batch.restype = ctypes.c_int
     L.fsdkr_modexp_nadic_batch.argtypes = L.fsdkr_modexp_joint_batch.argtypes
     L.fsdkr_modexp_nadic_batch.restype = ctypes.c_int
+    L.fsdkr_modexp_joint3_batch.argtypes = [vp, ctypes.c_uint32, u32p, u32p, u32p, ctypes.c_uint32, u32p, u32p, u32p,
+                                            u32p, u32p, ctypes.c_uint32, ctypes.c_uint32, u32p]
+    L.fsdkr_modexp_joint3_batch.restype = ctypes.c_int
+    L.fsdkr_bob_verify.argtypes = [vp, ctypes.POINTER(BobBatchC), u8p]
+    L.fsdkr_bob_verify.restype = ctypes.c_int
+    L.fsdkr_bob_verify_unfused.argtypes = L.fsdkr_bob_verify.argtypes
+    L.fsdkr_bob_verify_unfused.restype = ctypes.c_int
     L.fsdkr_modexp_batch_ct.restype = ctypes.c_int
     L.fsdkr_modexp_batch_device.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, ctypes.c_uint32,
                                             ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp]
@@ -329,6 +343,38 @@ class Context:
         self.check(self._lib.fsdkr_modexp_nadic_batch(self._h, count, _ptr(B), _ptr(B2), _ptr(E2), _ptr(I), _ptr(Mo),
                                                       _ptr(ME), exp_limbs, len(nmods), _ptr(O)))
         return limbs_to_ints(O)
+
+    def modexp_joint3_batch(self, bases, bases2, exps2, bases3, exps3, mods, mod_exps, mod_idx):
+        """[bases[i] ^ mod_exps[k] * bases2[i] ^ exps2[i] * bases3[i] ^ exps3[i] mod mods[k]],
+        k = mod_idx[i], 4096-bit moduli, exps2 < 2^768, exps3 < 2^256, bases2 / bases3
+        reduced: the split chain of Bob's range proof (fsdkr_modexp_joint3_batch).
+        bases3 = exps3 = None: the two-base tail at the same split."""
+        count = len(bases)
+        if count == 0:
+            return []
+        exp_limbs = max(1, (max(e.bit_length() for e in mod_exps) + 31) // 32)
+        e2l = max(1, (max(e.bit_length() for e in exps2) + 31) // 32)
+        B = ints_to_limbs(bases, 128)
+        B2 = ints_to_limbs(bases2, 128)
+        E2 = ints_to_limbs(exps2, e2l)
+        B3 = ints_to_limbs(bases3, 128) if bases3 is not None else None
+        E3 = ints_to_limbs(exps3, 8) if exps3 is not None else None
+        Mo = ints_to_limbs(mods, 128)
+        ME = ints_to_limbs(mod_exps, exp_limbs)
+        I = np.ascontiguousarray(np.asarray(mod_idx, dtype=np.uint32))
+        O = np.zeros((count, 128), dtype=np.uint32)
+        self.check(self._lib.fsdkr_modexp_joint3_batch(self._h, count, _ptr(B), _ptr(B2), _ptr(E2), e2l,
+                                                       _ptr(B3) if B3 is not None else None,
+                                                       _ptr(E3) if E3 is not None else None, _ptr(I), _ptr(Mo),
+                                                       _ptr(ME), exp_limbs, len(mods), _ptr(O)))
+        return limbs_to_ints(O)
+
+    def bob_verify(self, batch, count, fused=True):
+        """fsdkr_bob_verify on a filled BobBatchC -> uint8 verdicts (1 / 0 / 2 = panic)."""
+        out = np.zeros(count, dtype=np.uint8)
+        fn = self._lib.fsdkr_bob_verify if fused else self._lib.fsdkr_bob_verify_unfused
+        self.check(fn(self._h, ctypes.byref(batch), out.ctypes.data_as(u8p)))
+        return out
 
     def fixed_base_modexp(self, bases, base_mod_idx, mods, base_idx, exps, mod_limbs):
         """[bases[base_idx[i]] ^ exps[i] mod mods[base_mod_idx[base_idx[i]]]] via the fixed-base engine."""

@@ -1,0 +1,236 @@
+"""Bob's MtA range proofs (range_proofs.rs:205-590) on the MI355X engine: the
+respondent's proofs of GG20's MtA (BobProof) and MtA with check (BobProofExt).
+
+verify_bob   `count` independent proofs in one device pass (fsdkr_bob_verify):
+             the four h1 / h2 powers as fixed-base combs, z^e and t^e with one
+             simultaneous inversion, a_enc^s1 * s^N * mta^-e mod N^2 as ONE split
+             chain of 2048 squarings, the transcript hash and, for the extended
+             proof, G*s1 == X*e + u.
+generate_bob the prover (BobZkpRound1 / Round2, BobProof::generate), batched
+             per round over the existing entry points; secret exponents run
+             through the regular-access kernel."""
+import math
+
+import numpy as np
+
+from . import _native
+from .batch import UnsupportedInput, _limbs_for, pack, pack_points
+from .refresh import GX, GY, Q, FsDkrPanic, _ctx
+from .types import BobProof, BobProofExt
+
+PANIC = 2          # verdict: the reference panics (X or u at infinity, range_proofs.rs:428-431)
+Q3 = Q ** 3
+NL = 64            # limbs of N, N~ (2048-bit keys)
+_u32p = _native.u32p
+
+
+def _fits(name, values, limbs):
+    for v in values:
+        if v < 0:
+            raise UnsupportedInput(f"{name}: negative value")
+        if v.bit_length() > 32 * limbs:
+            raise UnsupportedInput(f"{name}: wider than {32 * limbs} bits")
+
+
+def key_table(eks, statements):
+    """Dedup the (ek, statement) pairs: (keys, key_idx) with keys a list of
+    (N, N~, h1, h2) and key_idx[p] the row of proof p."""
+    rows, keys, idx = {}, [], []
+    for ek, st in zip(eks, statements):
+        k = (ek.n, st.N, st.g, st.ni)
+        if k not in rows:
+            rows[k] = len(keys)
+            keys.append(k)
+        idx.append(rows[k])
+    return keys, idx
+
+
+def prepass(proofs, a_encs, mta_outs, eks, statements, X=None):
+    """The host pre-pass of verify_bob: validation, key dedup and the values the
+    device reads.  Returns a dict of ints / lists (packed by verify_bob):
+    keys, key_idx, the proof fields with s1 and e clamped to their packed widths,
+    and t1_red = t1 mod N (what the device multiplies into 1 + t1*N mod N^2)."""
+    count = len(proofs)
+    if not (len(a_encs) == len(mta_outs) == len(eks) == len(statements) == count):
+        raise ValueError("verify_bob: argument lists differ in length")
+    ext = X is not None
+    if ext and len(X) != count:
+        raise ValueError("verify_bob: X differs in length")
+    inner = [p.proof for p in proofs] if ext else list(proofs)
+    for ek, st in zip(eks, statements):
+        for name, v in (("N", ek.n), ("Ntilde", st.N)):
+            if v <= 0 or v % 2 == 0:
+                raise UnsupportedInput(f"{name}: even, zero or negative modulus (the verifier's own key)")
+    keys, key_idx = key_table(eks, statements)
+    for name, col, limbs in (("N", 0, NL), ("Ntilde", 1, NL), ("h1", 2, NL), ("h2", 3, NL)):
+        _fits(name, [k[col] for k in keys], limbs)
+    _fits("a_enc", a_encs, 2 * NL)
+    _fits("mta_out", mta_outs, 2 * NL)
+    for f in ("z", "t", "s"):
+        _fits(f, [getattr(p, f) for p in inner], NL)
+    for f in ("e", "s1", "s2", "t1", "t2"):
+        if any(getattr(p, f) < 0 for p in inner):
+            raise UnsupportedInput(f"{f}: negative value")
+    # s1 > q^3 is rejected whatever its size, a challenge of 2^256 or more never
+    # equals the hash: both are packed as the smallest value with that outcome
+    s1 = [min(p.s1, Q3 + 1) for p in inner]
+    e = [min(p.e, 1 << 256) for p in inner]
+    t1_red = [p.t1 % ek.n for p, ek in zip(inner, eks)]
+    return {"count": count, "ext": ext, "keys": keys, "key_idx": key_idx, "inner": inner, "s1": s1, "e": e,
+            "t1_red": t1_red, "s1_over": [p.s1 > Q3 for p in inner]}
+
+
+def _batch(pp, a_encs, mta_outs, proofs, X):
+    inner, count = pp["inner"], pp["count"]
+    keep = []
+
+    def arr(values, limbs):
+        a = pack(list(values), limbs)
+        keep.append(a)
+        return a.ctypes.data_as(_u32p)
+
+    def width(values):
+        return _limbs_for(max(1, max(v.bit_length() for v in values)))
+
+    b = _native.BobBatchC()
+    b.count, b.n_keys, b.nl = count, len(pp["keys"]), NL
+    s2, t1, t2 = [p.s2 for p in inner], [p.t1 for p in inner], [p.t2 for p in inner]
+    b.el, b.s1l, b.s2l, b.t1l, b.t2l = width(pp["e"]), width(pp["s1"]), width(s2), width(t1), width(t2)
+    for col, name in enumerate(("N", "Ntilde", "h1", "h2")):
+        setattr(b, name, arr([k[col] for k in pp["keys"]], NL))
+    ki = np.ascontiguousarray(np.asarray(pp["key_idx"], dtype=np.uint32))
+    keep.append(ki)
+    b.key_idx = ki.ctypes.data_as(_u32p)
+    b.a_enc, b.mta = arr(a_encs, 2 * NL), arr(mta_outs, 2 * NL)
+    b.z, b.t, b.s = (arr([getattr(p, f) for p in inner], NL) for f in ("z", "t", "s"))
+    b.e, b.s1 = arr(pp["e"], b.el), arr(pp["s1"], b.s1l)
+    b.s2, b.t1, b.t2 = arr(s2, b.s2l), arr(t1, b.t1l), arr(t2, b.t2l)
+    if pp["ext"]:
+        px, pu = pack_points(list(X)), pack_points([p.u for p in proofs])
+        keep += [px, pu]
+        b.X, b.u = px.ctypes.data_as(_u32p), pu.ctypes.data_as(_u32p)
+    return b, keep
+
+
+def verify_bob(proofs, a_encs, mta_outs, eks, statements, X=None, ctx=None, fused=True):
+    """BobProof::verify (range_proofs.rs:360-446) of every proof, or with X (one
+    point per proof, None = infinity) BobProofExt::verify (:527-562) of
+    BobProofExt objects.  eks / statements: the verifier's Paillier key and
+    (N~, h1, h2) per proof; equal pairs share one row of the device's key table.
+
+    Returns np.uint8[count]: 1 accepted, 0 rejected, PANIC (2) where the
+    reference panics (X or u at infinity, after the checks before the hash pass).
+
+    Raises batch.UnsupportedInput for what the C ABI does not represent: a
+    negative field; an even, zero or negative N or N~ (the verifier's own keys);
+    a hashed value wider than its field (N, N~, h1, h2, z, t, s above 2048 bits,
+    a_enc, mta_out above 4096 bits).  The reference's own outcome for these
+    (a panic in mod_pow for a negative exponent, a plain rejection otherwise) is
+    not reproduced per instance.  2048-bit keys.
+
+    fused=False runs the mod-N^2 part as three separate chains (A/B timing)."""
+    pp = prepass(proofs, a_encs, mta_outs, eks, statements, X)
+    if pp["count"] == 0:
+        return np.zeros(0, dtype=np.uint8)
+    b, keep = _batch(pp, a_encs, mta_outs, proofs, X)
+    out = _ctx(ctx).bob_verify(b, pp["count"], fused=fused)
+    del keep
+    return out
+
+
+def _from_modulo(rng, n):
+    """SampleFromMultiplicativeGroup::from_modulo (range_proofs.rs:599-607)."""
+    while True:
+        r = rng.sample_below(n)
+        if math.gcd(r, n) == 1:
+            return r
+
+
+def _challenge(ek, a_enc, mta, z, z_prim, t, v, w, check):
+    from .distribute import chain_bigint
+    vals = [ek.n, ek.n + 1, a_enc, mta, z, z_prim, t, v, w]
+    if check is not None:
+        for pt in check:
+            if pt is None:
+                raise FsDkrPanic("x_coord().unwrap() on the point at infinity (range_proofs.rs:486-489)")
+            vals += [pt[0], pt[1]]
+    return chain_bigint(*vals)
+
+
+def generate_bob(items, rng, ctx=None, check=False):
+    """BobProof::generate (range_proofs.rs:448-515) / BobProofExt::generate
+    (:564-589) for every item (a_enc, mta_out, b, beta_prim, ek, statement, r):
+    Alice's ciphertext, the MtA output, Bob's secret scalar b in [0, q), the
+    beta' and randomness r of Enc(beta'; r), and the verifier's keys.
+
+    Per proof the draws go through `rng` (sample_below) in the reference's order:
+    alpha, beta (from_modulo), gamma, ro, ro_prim, sigma, tau (:266-272).  The
+    exponentiations of all proofs are batched per round; every one with a secret
+    exponent runs through the regular-access kernel.  Returns BobProofs, or
+    BobProofExts with check=True."""
+    ctx = _ctx(ctx)
+    items = list(items)
+    n = len(items)
+    if n == 0:
+        return []
+    rnd = []
+    for a_enc, mta, b, beta_prim, ek, st, r in items:
+        alpha = rng.sample_below(Q3)
+        beta = _from_modulo(rng, ek.n)
+        gamma = rng.sample_below(Q * Q * ek.n)
+        ro = rng.sample_below(Q * st.N)
+        ro_prim = rng.sample_below(Q3 * st.N)
+        sigma = rng.sample_below(Q * st.N)
+        tau = rng.sample_below(Q3 * st.N)
+        rnd.append((alpha, beta, gamma, ro, ro_prim, sigma, tau))
+    # round 1: h1^(b, alpha, beta', gamma), h2^(ro, ro', sigma, tau) mod N~; a_enc^alpha, beta^N mod N^2
+    nts, nt_row = [], {}
+    nns, nn_row = [], {}
+    for _, _, _, _, ek, st, _ in items:
+        if st.N not in nt_row:
+            nt_row[st.N] = len(nts)
+            nts.append(st.N)
+        if ek.nn not in nn_row:
+            nn_row[ek.nn] = len(nns)
+            nns.append(ek.nn)
+    bases, exps, idx = [], [], []
+    for (a_enc, mta, b, beta_prim, ek, st, r), (alpha, beta, gamma, ro, ro_prim, sigma, tau) in zip(items, rnd):
+        for base, ex in ((st.g, b), (st.ni, ro), (st.g, alpha), (st.ni, ro_prim), (st.g, beta_prim), (st.ni, sigma),
+                         (st.g, gamma), (st.ni, tau)):
+            bases.append(base % st.N)
+            exps.append(ex)
+            idx.append(nt_row[st.N])
+    pw = ctx.modexp_batch(bases, exps, nts, idx, NL, secret=True)
+    va = ctx.modexp_batch([it[0] % it[4].nn for it in items], [x[0] for x in rnd], nns,
+                          [nn_row[it[4].nn] for it in items], 2 * NL, secret=True)
+    bn = ctx.modexp_batch([x[1] for x in rnd], [it[4].n for it in items], nns, [nn_row[it[4].nn] for it in items],
+                          2 * NL)   # beta^N: public exponent
+    pts = None
+    if check:   # X = G*b, u = G*alpha (:480-484)
+        g = (GX, GY)
+        pts = ctx.ec_msm([[g] for _ in range(2 * n)], [[it[2] % Q] for it in items] + [[x[0] % Q] for x in rnd])
+    es, firsts = [], []
+    for k, ((a_enc, mta, b, beta_prim, ek, st, r), x) in enumerate(zip(items, rnd)):
+        p = pw[8 * k:8 * k + 8]
+        z, z_prim = p[0] * p[1] % st.N, p[2] * p[3] % st.N
+        t, w = p[4] * p[5] % st.N, p[6] * p[7] % st.N
+        v = va[k] * (x[2] * ek.n + 1) * bn[k] % ek.nn
+        chk = (pts[k], pts[n + k]) if check else None
+        es.append(_challenge(ek, a_enc, mta, z, z_prim, t, v, w, chk))
+        firsts.append((t, z))
+    # round 2: r^e mod N (:328)
+    ns, n_row = [], {}
+    for it in items:
+        if it[4].n not in n_row:
+            n_row[it[4].n] = len(ns)
+            ns.append(it[4].n)
+    re = ctx.modexp_batch([it[6] % it[4].n for it in items], es, ns, [n_row[it[4].n] for it in items], NL)   # public e
+    out = []
+    for k, ((a_enc, mta, b, beta_prim, ek, st, r), x) in enumerate(zip(items, rnd)):
+        alpha, beta, gamma, ro, ro_prim, sigma, tau = x
+        e = es[k]
+        t, z = firsts[k]
+        pf = BobProof(t, z, e, re[k] * beta % ek.n, e * b + alpha, e * ro + ro_prim, e * beta_prim + gamma,
+                      e * sigma + tau)
+        out.append(BobProofExt(pf, pts[n + k]) if check else pf)
+    return out

@@ -49,6 +49,24 @@ class AliceProof:
 
 
 @dataclass(frozen=True)
+class BobProof:                    # range_proofs.rs:346-356
+    t: int
+    z: int
+    e: int
+    s: int
+    s1: int
+    s2: int
+    t1: int
+    t2: int
+
+
+@dataclass(frozen=True)
+class BobProofExt:                 # range_proofs.rs:520-523
+    proof: BobProof
+    u: Optional[Tuple[int, int]]
+
+
+@dataclass(frozen=True)
 class RingPedersenStatement:
     S: int
     T: int

@@ -314,6 +314,58 @@ int fsdkr_modexp_nadic_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* bas
                              const uint32_t* exp2, const uint32_t* mod_idx, const uint32_t* nmods,
                              const uint32_t* mod_exp, uint32_t exp_limbs, uint32_t n_mod, uint32_t* out);
 
+/* out[i] = base[i]^E[mod_idx[i]] * base2[i]^exp2[i] * base3[i]^exp3[i] mod
+ * mods[mod_idx[i]] (4096-bit odd moduli, 128 limbs; E as fsdkr_modexp_joint_batch;
+ * exp2: exp2_limbs <= 24 limbs, below 2^768; exp3: 8 limbs; base2, base3 reduced)
+ * in one chain: the head over E's bits >= 768, then the three-base tail.  This is
+ * how fsdkr_bob_verify computes s^N a_enc^s1 (mta^-1)^e mod N^2
+ * (range_proofs.rs:396-400).  base3 = exp3 = NULL: the two-base tail at the same
+ * split.  Parity tests of that path. */
+int fsdkr_modexp_joint3_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* base, const uint32_t* base2,
+                              const uint32_t* exp2, uint32_t exp2_limbs, const uint32_t* base3, const uint32_t* exp3,
+                              const uint32_t* mod_idx, const uint32_t* mods, const uint32_t* mod_exp,
+                              uint32_t exp_limbs, uint32_t n_mod, uint32_t* out);
+
+/* ---- Bob's MtA range proofs ------------------------------------------------
+ * BobProof::verify (range_proofs.rs:360-446) and BobProofExt::verify (:527-562)
+ * of `count` independent proofs in one device pass.  Little-endian u32 limbs,
+ * non-negative values.  The verifier's keys are a table of n_keys rows (N odd,
+ * Ntilde odd, nl = 64 limbs); key_idx[p] names the row of proof p.  Values at or
+ * above their modulus are reduced for the arithmetic and hashed as given.  t1 may
+ * be wider than N (the honest t1 is): 1 + t1 N is taken modulo N^2.
+ * X / u: affine secp256k1 points, 16 limbs (x | y), all zero = the point at
+ * infinity; both NULL: plain BobProof, both set: BobProofExt for every proof.
+ * verdict[p]: 1 accepted, 0 rejected, 2 the reference panics (X or u at infinity,
+ * :428-431, reached only when the checks before the hash pass). */
+typedef struct fsdkr_bob_batch {
+  uint32_t count, n_keys, nl;
+  uint32_t el, s1l, s2l, t1l, t2l;   /* limbs of e, s1, s2, t1, t2 (el, s1l <= 64) */
+  const uint32_t* N;        /* [n_keys][nl]  alice_ek.n            */
+  const uint32_t* Ntilde;   /* [n_keys][nl]  dlog_statement.N      */
+  const uint32_t* h1;       /* [n_keys][nl]  dlog_statement.g      */
+  const uint32_t* h2;       /* [n_keys][nl]  dlog_statement.ni     */
+  const uint32_t* key_idx;  /* [count]                             */
+  const uint32_t* a_enc;    /* [count][2nl]                        */
+  const uint32_t* mta;      /* [count][2nl]  mta_avc_out           */
+  const uint32_t* z;        /* [count][nl]                         */
+  const uint32_t* t;        /* [count][nl]                         */
+  const uint32_t* s;        /* [count][nl]                         */
+  const uint32_t* e;        /* [count][el]                         */
+  const uint32_t* s1;       /* [count][s1l]                        */
+  const uint32_t* s2;       /* [count][s2l]                        */
+  const uint32_t* t1;       /* [count][t1l]                        */
+  const uint32_t* t2;       /* [count][t2l]                        */
+  const uint32_t* X;        /* [count][16] or NULL                 */
+  const uint32_t* u;        /* [count][16] or NULL                 */
+} fsdkr_bob_batch;
+
+int fsdkr_bob_verify(fsdkr_ctx* ctx, const fsdkr_bob_batch* batch, uint8_t* verdict);
+
+/* The same verdicts with the mod-N^2 part as three separate chains (a_enc^s1, s^N,
+ * mta^e and its inverse) instead of the three-base tail: the A/B counterpart of
+ * fsdkr_bob_verify (tools/bench_mta.py), not a second implementation to call. */
+int fsdkr_bob_verify_unfused(fsdkr_ctx* ctx, const fsdkr_bob_batch* batch, uint8_t* verdict);
+
 /* Which prestarted parts the last fsdkr_collect_prepare[_multi] reused (bit
  * mask): 1 GA chains, 2 fixed-base tables, 4 correct-key job, 8 ring-Pedersen
  * T^Z exponents (multi-session).  0 before any prepare.  Diagnostic (tests
