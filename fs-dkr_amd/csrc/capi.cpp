@@ -332,9 +332,11 @@ int launch_modexp_desc(Ctx* c, uint32_t k32, uint32_t count, uint32_t exp_bits, 
   if (grp == kWaveGroup && k32 != 128) grp = 16;
   if (c->ct) grp = 0;   // the regular-access kernels have one shape per width
   // sliding windows: the 4096-bit 4/8/16/32-lane shapes, public exponents, waves of
-  // `group` lanes uniform (caller), so only at the caller's lane count
-  const bool slide = (desc_flags & kDescSlide) && (desc_flags & kDescOutIdx) && k32 == 128 && !c->ct &&
-                     grp == group && (grp == 4 || grp == 8 || grp == 16 || grp == kWideGroup);
+  // `group` lanes uniform (caller), so only at the caller's lane count; 6144-bit
+  // moduli have the 8-lane split chain only (head and tail), no whole-chain kernel
+  const bool slide_shape = k32 == 128 ? (grp == 4 || grp == 8 || grp == 16 || grp == kWideGroup)
+                                      : (k32 == 192 && grp == 8 && split && split->lo_bit && !split->nadic);
+  const bool slide = (desc_flags & kDescSlide) && (desc_flags & kDescOutIdx) && !c->ct && grp == group && slide_shape;
   const int KD = table_digits(k32, grp);
   if (!KD) {
     c->fail("unsupported modulus width %u limbs", k32);
@@ -371,7 +373,7 @@ int launch_modexp_desc(Ctx* c, uint32_t k32, uint32_t count, uint32_t exp_bits, 
   a.out_idx = (desc_flags & kDescOutIdx) ? reinterpret_cast<const uint32_t*>(d_desc + 2 * n8 + 4 * n4) : nullptr;
   if (split && split->lo_bit) {   // head / tail of split chains: the slide shapes at the caller's lanes
     if (!slide || grp != group || !(grp == 4 || grp == 8 || grp == 16 || grp == kWideGroup)) {
-      c->fail("split chains need the 4 / 8 / 16 / 32-lane sliding-window shapes (group %u)", grp);
+      c->fail("split chains need the 4 / 8 / 16 / 32-lane sliding-window shapes, 8 lanes at 192 limbs (group %u)", grp);
       return FSDKR_E_ARG;
     }
     const std::string base(table_tag);

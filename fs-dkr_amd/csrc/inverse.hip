@@ -422,11 +422,17 @@ size_t inverse_batch_scratch_words(uint32_t k32) {
   }
 }
 
+// The 96- and 192-limb shapes (3072-bit keys: Ñ and N^2) run in the lane shapes of
+// the other kernels of their widths, 26 radix-2^30 limbs per lane in the binary GCD;
+// scratch rows of shape_digits(k32) words.  Bob's MtA proofs use them (mta.cpp);
+// collect() keeps the per-element inverse at these widths (the function above).
 hipError_t launch_inverse_batch(uint32_t k32, const BatchInverseArgs& a, hipStream_t st) {
   if (!a.ngroups) return hipSuccess;
   switch (k32) {
     case 64: return launch_batch<72, 8, 64>(a, st);
+    case 96: return launch_batch<108, 4, 96>(a, st);
     case 128: return launch_batch<144, 8, 128>(a, st);
+    case 192: return launch_batch<216, 8, 192>(a, st);
     default: return hipErrorInvalidValue;
   }
 }

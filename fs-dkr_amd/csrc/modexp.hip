@@ -701,6 +701,9 @@ __global__ __launch_bounds__(BLOCK) void modexp_nadic_head_kernel(const ModexpAr
 // scaled, the 4-lane throughput shape plain).  Exact results.
 // J3: a second extra base (ModexpArgs base3_ptr): base3^exp3 rides the same
 // squarings over its own 16-entry table, 4-bit windows of exp3 below exp3_bits.
+// The 6144-bit shape <216, 8, 192> (Bob's chain for 3072-bit keys, mta.cpp) holds
+// 27 digits per lane; its entry code is ordered (ACC_LATE) so that nothing but the
+// working row is live across the table builds: 253 VGPRs (J3) / 234, no scratch.
 template <int KD, int G, int K32, bool QS, bool NA = false, bool J3 = false>
 __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs a) {
   using MT = Mont29<KD, G>;
@@ -737,9 +740,15 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs 
   const int exp_limbs = __builtin_amdgcn_readfirstlane((int)a.exp_len[inst]);
   auto bit = [&](int i) -> uint32_t { return (i >> 5) < exp_limbs ? (E[i >> 5] >> (i & 31)) & 1u : 0u; };
   const int lo = (int)a.lo_bit;
+  // the 6144-bit shape (L = 27) takes the head's accumulator after the joint tables
+  // are built: held across those products it went to scratch with the builds' state
+  constexpr bool ACC_LATE = K32 > 128;
+  static_assert(!(ACC_LATE && NA), "the N-adic entry converts the accumulator first");
   uint32_t acc[L];
+  if constexpr (!ACC_LATE) {
 #pragma unroll
-  for (int j = 0; j < L; ++j) acc[j] = a.state[(size_t)inst * KD + g * L + j];
+    for (int j = 0; j < L; ++j) acc[j] = a.state[(size_t)inst * KD + g * L + j];
+  }
   auto put_row = [&](const uint32_t* row) {
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -794,6 +803,7 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs 
   }
   // the joint base's table T2[u] = base2^u (Montgomery form), u < 16
   const bool joint = a.base2_ptr != nullptr;
+  uint32_t built = 0;   // a digit of the last T2 row (orders the J3 entry's reads after that build, ACC_LATE)
   uint32_t* T2 = joint ? a.table2 + (size_t)inst * 16 * KD : nullptr;
   const uint32_t* E2 = nullptr;
   uint32_t e2len = 0;
@@ -819,6 +829,7 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs 
 #pragma unroll
       for (int j = 0; j < L; ++j) T2[(size_t)u * KD + g * L + j] = y[j];
     }
+    built = y[0];
   }
   // the second extra base's table T3[u] = base3^u, u < 16
   uint32_t* T3 = nullptr;
@@ -832,13 +843,18 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs 
     e3len = a.exp3_len[inst];
     e3bits = (int)a.exp3_bits;
     const uint32_t* B3 = reinterpret_cast<const uint32_t*>(a.base3_ptr[inst]);
+    // this entry's limb offsets (and the rows 1, R^2) are made again here: kept
+    // from T2's entry, the 27 64-bit offsets sat in scratch across its build
+    const uint32_t* C3 = C;
+    int g3 = g;
+    if constexpr (ACC_LATE) asm volatile("" : "+v"(C3), "+v"(g3) : "v"(built));
     uint32_t y[L];
 #pragma unroll
     for (int j = 0; j < L; ++j) {
-      y[j] = digit_of(B3, K32, g * L + j);
-      T3[g * L + j] = C[KD + g * L + j];
+      y[j] = digit_of(B3, K32, g3 * L + j);
+      T3[g * L + j] = C3[KD + g * L + j];
     }
-    put_row(C + 2 * KD);
+    put_row(C3 + 2 * KD);
     mulx(y);
 #pragma unroll
     for (int j = 0; j < L; ++j) T3[KD + g * L + j] = y[j];
@@ -855,6 +871,10 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs 
   // T[d >> 1] in; every 4th bit the instance's exp2 digit multiplies T2[digit] in
   int pend_at = -1;
   uint32_t pend_d = 0, ew = 0;
+  if constexpr (ACC_LATE) {
+#pragma unroll
+    for (int j = 0; j < L; ++j) acc[j] = a.state[(size_t)inst * KD + g * L + j];
+  }
   for (int i = lo - 1; i >= 0; --i) {
     if ((i & 31) == 31 && joint) ew = ((uint32_t)(i >> 5) < e2len) ? E2[i >> 5] : 0u;
     if constexpr (J3) {
@@ -898,9 +918,12 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs 
   }
   // exit: acc * 1 / R modulo N itself
   if constexpr (QS) {
+    const uint32_t* CX = C0;
+    // N's row addresses are made here, not held from the entry through the loop
+    if constexpr (ACC_LATE) asm volatile("" : "+v"(CX) : "v"(acc[0]));
 #pragma unroll
-    for (int j = 0; j < L; ++j) M.n[j] = C0[g * L + j];
-    M.ninv = C0[3 * KD];
+    for (int j = 0; j < L; ++j) M.n[j] = CX[g * L + j];
+    M.ninv = CX[3 * KD];
   }
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -1159,6 +1182,16 @@ hipError_t modexp(uint32_t k32, const ModexpArgs& a, hipStream_t st) {
   // multiply per row) at every group shape: 8-32 lanes since round 4, the 4-lane
   // throughput shapes since round 5 (metric 2 -1.5 % keyed, -0.9 % per-instance
   // exponents, interleaved, profiles/r05/r05qs4_*)
+  if (a.slide && k32 == 192) {   // 6144-bit: the split chain only, at 8 lanes (L = 27), quotient-scaled
+    if (a.ct || a.group != 8 || !a.lo_bit || a.nadic || !a.state) return hipErrorInvalidValue;
+    if (!a.tail) return launch_modexp_slide<216, 8, 192, true>(a, st);
+    if (a.base3_ptr) {
+      if (!a.base2_ptr || !a.exp3_ptr || !a.exp3_len || !a.table3 || (a.exp3_bits & 3u) || a.exp3_bits > a.lo_bit)
+        return hipErrorInvalidValue;
+      return launch_modexp_tail<216, 8, 192, true, false, true>(a, st);
+    }
+    return launch_modexp_tail<216, 8, 192, true>(a, st);
+  }
   if (a.slide) {   // shared exponent per wave: the 4096-bit shapes of GA
     if (k32 != 128 || a.ct || a.group == kWaveGroup) return hipErrorInvalidValue;
     if (a.base3_ptr) {   // the three-base tail: after the full-width head, beside base2

@@ -1,5 +1,6 @@
 // Bob's MtA range proofs of the C ABI (include/fsdkr/fsdkr.h):
 //   fsdkr_modexp_joint3_batch   parity entry of the three-base tail (modexp.hip modexp_tail_kernel J3)
+//   fsdkr_modexp_joint3_batch_k the same at a modulus width of 128 or 192 limbs
 //   fsdkr_bob_verify            BobProof::verify (range_proofs.rs:360-446) and
 //                               BobProofExt::verify (:527-562), `count` proofs in one pass
 //   fsdkr_bob_verify_unfused    the same verdicts with three separate mod-N^2 chains (A/B)
@@ -9,9 +10,11 @@
 // (:413-441); with X / u the curve equation G s1 == X e + u (:550-559).
 // The pieces: fixed-base combs for the four h1 / h2 powers (bases shared per key),
 // a 256-bit modexp job for z^e | t^e, Montgomery's simultaneous inversion, and for
-// s^N a_enc^s1 (mta^-1)^e ONE split chain of 2048 squarings: the head over N's
+// s^N a_enc^s1 (mta^-1)^e ONE split chain of bits(N) squarings: the head over N's
 // bits >= 768, the tail with a_enc (4-bit windows of s1 < 2^768) and mta^-1
-// (windows of e < 2^256) riding its squarings.
+// (windows of e < 2^256) riding its squarings.  Two width classes, one per batch:
+// nl = 64 (keys up to 2048 bits, N^2 of 128 limbs, 4 / 8 / 16 lanes per chain) and
+// nl = 96 (up to 3072 bits, N^2 of 192 limbs, the 8-lane split chain).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -78,12 +81,20 @@ void inverse_groups(const uint32_t* key, uint32_t reps, uint32_t count, uint32_t
 }
 
 // lanes per chain of the split launch: a forced context setting (tests, tuning)
-// where the tail has that shape, else by batch size
-int split_group(Ctx* c, const char* who, uint32_t count, bool wide_ok, uint32_t* group) {
+// where the tail has that shape, else by batch size; 192-limb moduli: 8 lanes
+int split_group(Ctx* c, const char* who, uint32_t count, bool wide_ok, uint32_t k32, uint32_t* group) {
   const uint32_t f = c->modexp_group;
   if (c->ct) {
     c->fail("%s: public exponents only (constant-time context)", who);
     return FSDKR_E_ARG;
+  }
+  if (k32 == 192) {
+    if (f != 0 && f != 8) {
+      c->fail("%s: the 6144-bit split chains run at 8 lanes (forced %u)", who, f);
+      return FSDKR_E_ARG;
+    }
+    *group = 8;
+    return FSDKR_OK;
   }
   if (f == 0) *group = keyed_lanes(count);   // as the keyed 4096-bit launches pick their lanes
   else if (f == 4 || f == 8 || f == 16 || (wide_ok && f == kWideGroup)) *group = f;
@@ -98,15 +109,19 @@ int split_group(Ctx* c, const char* who, uint32_t count, bool wide_ok, uint32_t*
 
 extern "C" {
 
-int fsdkr_modexp_joint3_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* base, const uint32_t* base2,
-                              const uint32_t* exp2, uint32_t exp2_limbs, const uint32_t* base3, const uint32_t* exp3,
-                              const uint32_t* mod_idx, const uint32_t* mods, const uint32_t* mod_exp,
-                              uint32_t exp_limbs, uint32_t n_mod, uint32_t* out) {
+int fsdkr_modexp_joint3_batch_k(fsdkr_ctx* ctx, uint32_t k32, uint32_t count, const uint32_t* base,
+                                const uint32_t* base2, const uint32_t* exp2, uint32_t exp2_limbs, const uint32_t* base3,
+                                const uint32_t* exp3, const uint32_t* mod_idx, const uint32_t* mods,
+                                const uint32_t* mod_exp, uint32_t exp_limbs, uint32_t n_mod, uint32_t* out) {
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
   if (!c) return FSDKR_E_ARG;
-  if (count == 0) return FSDKR_OK;
   const char* who = "fsdkr_modexp_joint3_batch";
-  constexpr uint32_t K = 128;
+  if (k32 != 128 && k32 != 192) {
+    c->fail("%s: unsupported modulus width %u limbs", who, k32);
+    return FSDKR_E_UNSUPPORTED;
+  }
+  if (count == 0) return FSDKR_OK;
+  const uint32_t K = k32;
   if (!base || !base2 || !exp2 || !mod_idx || !mods || !mod_exp || !out || !n_mod || !exp_limbs || !exp2_limbs ||
       exp2_limbs > kS1Limbs || (base3 == nullptr) != (exp3 == nullptr)) {
     c->fail("%s: bad argument", who);
@@ -127,7 +142,7 @@ int fsdkr_modexp_joint3_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* ba
     }
   uint32_t group = 16;
   int rc;
-  if ((rc = split_group(c, who, count, true, &group))) return rc;
+  if ((rc = split_group(c, who, count, true, K, &group))) return rc;
   const uint32_t per_wave = 64 / group;
   const size_t cap = (size_t)count + (size_t)n_mod * per_wave;
   size_t off = 0;
@@ -192,6 +207,14 @@ int fsdkr_modexp_joint3_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* ba
   return c->sync();
 }
 
+int fsdkr_modexp_joint3_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* base, const uint32_t* base2,
+                              const uint32_t* exp2, uint32_t exp2_limbs, const uint32_t* base3, const uint32_t* exp3,
+                              const uint32_t* mod_idx, const uint32_t* mods, const uint32_t* mod_exp,
+                              uint32_t exp_limbs, uint32_t n_mod, uint32_t* out) {
+  return fsdkr_modexp_joint3_batch_k(ctx, 128, count, base, base2, exp2, exp2_limbs, base3, exp3, mod_idx, mods, mod_exp,
+                                     exp_limbs, n_mod, out);
+}
+
 static int bob_verify_impl(Ctx* c, const char* who, const fsdkr_bob_batch* b, uint8_t* verdict, bool fused) {
   if (!b) {
     c->fail("%s: null batch", who);
@@ -205,10 +228,12 @@ static int bob_verify_impl(Ctx* c, const char* who, const fsdkr_bob_batch* b, ui
     c->fail("%s: bad argument", who);
     return FSDKR_E_ARG;
   }
-  if (nl != 64) {
+  if (nl != 64 && nl != 96) {
     c->fail("%s: unsupported modulus width %u limbs", who, nl);
     return FSDKR_E_UNSUPPORTED;
   }
+  // digits per row of the inversion scratch: the kernels' shapes of both widths
+  const size_t kdl = (size_t)shape_digits(nl), kdn = (size_t)shape_digits(nn);
   const bool ext = b->X != nullptr;
   for (uint32_t k = 0; k < nk; ++k) {
     const uint32_t *N = b->N + (size_t)k * nl, *Nt = b->Ntilde + (size_t)k * nl;
@@ -224,7 +249,7 @@ static int bob_verify_impl(Ctx* c, const char* who, const fsdkr_bob_batch* b, ui
     }
   uint32_t group = 16;
   int rc;
-  if ((rc = split_group(c, who, count, false, &group))) return rc;
+  if ((rc = split_group(c, who, count, false, nn, &group))) return rc;
   const uint32_t* key = b->key_idx;
 
   // ---- host pre-pass -------------------------------------------------------
@@ -313,7 +338,7 @@ static int bob_verify_impl(Ctx* c, const char* who, const fsdkr_bob_batch* b, ui
   const size_t o_un = take(fused ? 0 : 3 * C * rn);   // unfused: a_enc^s1 | mta^e | (mta^e)^-1
   const size_t o_v0 = take(fused ? 0 : C * rn), o_p3u = take(fused ? 0 : C * sizeof(Prod3Operand));
   const size_t o_zw = take(2 * C * rl), o_v = take(C * rn);
-  const size_t o_iscr = take(2 * C * 144 * 4);
+  const size_t o_iscr = take(C * (kdn + 2 * kdl) * 4);
   uint8_t* dev = (uint8_t*)c->buf("bob_io", off);
   if (!dev) {
     c->fail("%s: device allocation failed (%zu bytes)", who, off);
@@ -446,7 +471,7 @@ static int bob_verify_impl(Ctx* c, const char* who, const fsdkr_bob_batch* b, ui
   uint32_t *cons_nl = nullptr, *cons_nn = nullptr;
   if ((rc = setup_moduli(c, nl, PU(o_Nt), nk, &cons_nl, "bob_nl")) || (rc = setup_moduli(c, nn, PU(o_NN), nk, &cons_nn, "bob_nn")))
     return rc;
-  uint32_t* iscr = PU(o_iscr);   // [C][144] for the N^2 inverse, then [2C][72] for the N~ ones
+  uint32_t* iscr = PU(o_iscr);   // [C][kdn] for the N^2 inverse, then [2C][kdl] for the N~ ones
   hipEvent_t ready = nullptr, side_done = nullptr;
   auto drop = [&](int r) {
     if (ready) (void)hipEventDestroy(ready);
@@ -482,7 +507,8 @@ static int bob_verify_impl(Ctx* c, const char* who, const fsdkr_bob_batch* b, ui
         (rc = launch_modexp_desc(c, nn, gn, nbits, dev + o_gdesc, cons_nn, PU(o_ga), st, "mxt_bob", 0, group, flags, &tail)))
       return drop(rc);
   } else {
-    // s^N (keyed sliding windows), a_enc^s1, mta^e and its inverse, then their product
+    // s^N (keyed sliding windows; at 192 limbs the general kernel's fixed windows, as the
+    // other two), a_enc^s1, mta^e and its inverse, then their product
     if ((rc = launch_modexp_desc(c, nn, gn, nbits, dev + o_gdesc, cons_nn, PU(o_ga), st, "mxt_bob", 0, group, flags)) ||
         (rc = launch_modexp_desc(c, nn, count, Ju.exp_bits, dev + o_udesc, cons_nn, PU(o_un), st, "mxt_bob_u")) ||
         (rc = launch_modexp_desc(c, nn, count, kEBits, dev + o_udesc + al256(Ju.desc_bytes()), cons_nn,
@@ -501,7 +527,7 @@ static int bob_verify_impl(Ctx* c, const char* who, const fsdkr_bob_batch* b, ui
     if ((rc = launch_modexp_desc(c, nl, 2 * count, kEBits, dev + o_zdesc, cons_nl, PU(o_zte), ss, "mxt_bob_z")))
       return drop(rc);
     BatchInverseArgs a{(const uint64_t*)(dev + o_iy) + C, (const uint64_t*)(dev + o_im) + C, PU(o_iord) + C,
-                       PU(o_igs) + igs_nl, PU(o_ztinv), PU(o_uzt), iscr + C * 144, (uint32_t)gs_nl.size() - 1};
+                       PU(o_igs) + igs_nl, PU(o_ztinv), PU(o_uzt), iscr + C * kdn, (uint32_t)gs_nl.size() - 1};
     c->mark("inverse", true);
     rc = c->hip_check(launch_inverse_batch(nl, a, ss), "inverse nl");
     c->mark("inverse", false);

@@ -143,6 +143,8 @@ def lib():
     L.fsdkr_modexp_joint3_batch.argtypes = [vp, ctypes.c_uint32, u32p, u32p, u32p, ctypes.c_uint32, u32p, u32p, u32p,
                                             u32p, u32p, ctypes.c_uint32, ctypes.c_uint32, u32p]
     L.fsdkr_modexp_joint3_batch.restype = ctypes.c_int
+    L.fsdkr_modexp_joint3_batch_k.argtypes = [vp, ctypes.c_uint32] + L.fsdkr_modexp_joint3_batch.argtypes[1:]
+    L.fsdkr_modexp_joint3_batch_k.restype = ctypes.c_int
     L.fsdkr_bob_verify.argtypes = [vp, ctypes.POINTER(BobBatchC), u8p]
     L.fsdkr_bob_verify.restype = ctypes.c_int
     L.fsdkr_bob_verify_unfused.argtypes = L.fsdkr_bob_verify.argtypes
@@ -344,29 +346,30 @@ class Context:
                                                       _ptr(ME), exp_limbs, len(nmods), _ptr(O)))
         return limbs_to_ints(O)
 
-    def modexp_joint3_batch(self, bases, bases2, exps2, bases3, exps3, mods, mod_exps, mod_idx):
+    def modexp_joint3_batch(self, bases, bases2, exps2, bases3, exps3, mods, mod_exps, mod_idx, k32=128):
         """[bases[i] ^ mod_exps[k] * bases2[i] ^ exps2[i] * bases3[i] ^ exps3[i] mod mods[k]],
-        k = mod_idx[i], 4096-bit moduli, exps2 < 2^768, exps3 < 2^256, bases2 / bases3
-        reduced: the split chain of Bob's range proof (fsdkr_modexp_joint3_batch).
-        bases3 = exps3 = None: the two-base tail at the same split."""
+        k = mod_idx[i], moduli of k32 limbs (128: 4096 bits, 192: 6144 bits), exps2 < 2^768,
+        exps3 < 2^256, bases2 / bases3 reduced: the split chain of Bob's range proof
+        (fsdkr_modexp_joint3_batch_k).  bases3 = exps3 = None: the two-base tail at the
+        same split."""
         count = len(bases)
         if count == 0:
             return []
         exp_limbs = max(1, (max(e.bit_length() for e in mod_exps) + 31) // 32)
         e2l = max(1, (max(e.bit_length() for e in exps2) + 31) // 32)
-        B = ints_to_limbs(bases, 128)
-        B2 = ints_to_limbs(bases2, 128)
+        B = ints_to_limbs(bases, k32)
+        B2 = ints_to_limbs(bases2, k32)
         E2 = ints_to_limbs(exps2, e2l)
-        B3 = ints_to_limbs(bases3, 128) if bases3 is not None else None
+        B3 = ints_to_limbs(bases3, k32) if bases3 is not None else None
         E3 = ints_to_limbs(exps3, 8) if exps3 is not None else None
-        Mo = ints_to_limbs(mods, 128)
+        Mo = ints_to_limbs(mods, k32)
         ME = ints_to_limbs(mod_exps, exp_limbs)
         I = np.ascontiguousarray(np.asarray(mod_idx, dtype=np.uint32))
-        O = np.zeros((count, 128), dtype=np.uint32)
-        self.check(self._lib.fsdkr_modexp_joint3_batch(self._h, count, _ptr(B), _ptr(B2), _ptr(E2), e2l,
-                                                       _ptr(B3) if B3 is not None else None,
-                                                       _ptr(E3) if E3 is not None else None, _ptr(I), _ptr(Mo),
-                                                       _ptr(ME), exp_limbs, len(mods), _ptr(O)))
+        O = np.zeros((count, k32), dtype=np.uint32)
+        self.check(self._lib.fsdkr_modexp_joint3_batch_k(self._h, k32, count, _ptr(B), _ptr(B2), _ptr(E2), e2l,
+                                                         _ptr(B3) if B3 is not None else None,
+                                                         _ptr(E3) if E3 is not None else None, _ptr(I), _ptr(Mo),
+                                                         _ptr(ME), exp_limbs, len(mods), _ptr(O)))
         return limbs_to_ints(O)
 
     def bob_verify(self, batch, count, fused=True):

@@ -4,8 +4,9 @@ respondent's proofs of GG20's MtA (BobProof) and MtA with check (BobProofExt).
 verify_bob   `count` independent proofs in one device pass (fsdkr_bob_verify):
              the four h1 / h2 powers as fixed-base combs, z^e and t^e with one
              simultaneous inversion, a_enc^s1 * s^N * mta^-e mod N^2 as ONE split
-             chain of 2048 squarings, the transcript hash and, for the extended
-             proof, G*s1 == X*e + u.
+             chain of bits(N) squarings, the transcript hash and, for the extended
+             proof, G*s1 == X*e + u.  Keys of up to 2048 bits run in the 64-limb
+             class, keys of up to 3072 bits in the 96-limb class (one per call).
 generate_bob the prover (BobZkpRound1 / Round2, BobProof::generate), batched
              per round over the existing entry points; secret exponents run
              through the regular-access kernel."""
@@ -20,7 +21,8 @@ from .types import BobProof, BobProofExt
 
 PANIC = 2          # verdict: the reference panics (X or u at infinity, range_proofs.rs:428-431)
 Q3 = Q ** 3
-NL = 64            # limbs of N, N~ (2048-bit keys)
+NL = 64            # limbs of N, N~ in the class of 2048-bit keys
+NL_CLASSES = (64, 96)   # width classes of a call: keys of up to 2048 / 3072 bits
 _u32p = _native.u32p
 
 
@@ -30,6 +32,17 @@ def _fits(name, values, limbs):
             raise UnsupportedInput(f"{name}: negative value")
         if v.bit_length() > 32 * limbs:
             raise UnsupportedInput(f"{name}: wider than {32 * limbs} bits")
+
+
+def width_class(eks, statements):
+    """Limbs of N, N~ for a call: the smallest class that fits every N and N~ (the
+    keys alone decide; a proof field wider than its place in that class is not
+    representable, see verify_bob)."""
+    bits = max([1] + [v.bit_length() for ek, st in zip(eks, statements) for v in (ek.n, st.N)])
+    for nl in NL_CLASSES:
+        if bits <= 32 * nl:
+            return nl
+    raise UnsupportedInput(f"N / Ntilde: wider than {32 * NL_CLASSES[-1]} bits")
 
 
 def key_table(eks, statements):
@@ -48,8 +61,9 @@ def key_table(eks, statements):
 def prepass(proofs, a_encs, mta_outs, eks, statements, X=None):
     """The host pre-pass of verify_bob: validation, key dedup and the values the
     device reads.  Returns a dict of ints / lists (packed by verify_bob):
-    keys, key_idx, the proof fields with s1 and e clamped to their packed widths,
-    and t1_red = t1 mod N (what the device multiplies into 1 + t1*N mod N^2)."""
+    keys, key_idx, nl (the call's width class, width_class), the proof fields with
+    s1 and e clamped to their packed widths, and t1_red = t1 mod N (what the device
+    multiplies into 1 + t1*N mod N^2)."""
     count = len(proofs)
     if not (len(a_encs) == len(mta_outs) == len(eks) == len(statements) == count):
         raise ValueError("verify_bob: argument lists differ in length")
@@ -62,12 +76,13 @@ def prepass(proofs, a_encs, mta_outs, eks, statements, X=None):
             if v <= 0 or v % 2 == 0:
                 raise UnsupportedInput(f"{name}: even, zero or negative modulus (the verifier's own key)")
     keys, key_idx = key_table(eks, statements)
-    for name, col, limbs in (("N", 0, NL), ("Ntilde", 1, NL), ("h1", 2, NL), ("h2", 3, NL)):
+    nl = width_class(eks, statements)
+    for name, col, limbs in (("N", 0, nl), ("Ntilde", 1, nl), ("h1", 2, nl), ("h2", 3, nl)):
         _fits(name, [k[col] for k in keys], limbs)
-    _fits("a_enc", a_encs, 2 * NL)
-    _fits("mta_out", mta_outs, 2 * NL)
+    _fits("a_enc", a_encs, 2 * nl)
+    _fits("mta_out", mta_outs, 2 * nl)
     for f in ("z", "t", "s"):
-        _fits(f, [getattr(p, f) for p in inner], NL)
+        _fits(f, [getattr(p, f) for p in inner], nl)
     for f in ("e", "s1", "s2", "t1", "t2"):
         if any(getattr(p, f) < 0 for p in inner):
             raise UnsupportedInput(f"{f}: negative value")
@@ -76,12 +91,12 @@ def prepass(proofs, a_encs, mta_outs, eks, statements, X=None):
     s1 = [min(p.s1, Q3 + 1) for p in inner]
     e = [min(p.e, 1 << 256) for p in inner]
     t1_red = [p.t1 % ek.n for p, ek in zip(inner, eks)]
-    return {"count": count, "ext": ext, "keys": keys, "key_idx": key_idx, "inner": inner, "s1": s1, "e": e,
+    return {"count": count, "ext": ext, "keys": keys, "key_idx": key_idx, "nl": nl, "inner": inner, "s1": s1, "e": e,
             "t1_red": t1_red, "s1_over": [p.s1 > Q3 for p in inner]}
 
 
 def _batch(pp, a_encs, mta_outs, proofs, X):
-    inner, count = pp["inner"], pp["count"]
+    inner, count, nl = pp["inner"], pp["count"], pp["nl"]
     keep = []
 
     def arr(values, limbs):
@@ -93,16 +108,16 @@ def _batch(pp, a_encs, mta_outs, proofs, X):
         return _limbs_for(max(1, max(v.bit_length() for v in values)))
 
     b = _native.BobBatchC()
-    b.count, b.n_keys, b.nl = count, len(pp["keys"]), NL
+    b.count, b.n_keys, b.nl = count, len(pp["keys"]), nl
     s2, t1, t2 = [p.s2 for p in inner], [p.t1 for p in inner], [p.t2 for p in inner]
     b.el, b.s1l, b.s2l, b.t1l, b.t2l = width(pp["e"]), width(pp["s1"]), width(s2), width(t1), width(t2)
     for col, name in enumerate(("N", "Ntilde", "h1", "h2")):
-        setattr(b, name, arr([k[col] for k in pp["keys"]], NL))
+        setattr(b, name, arr([k[col] for k in pp["keys"]], nl))
     ki = np.ascontiguousarray(np.asarray(pp["key_idx"], dtype=np.uint32))
     keep.append(ki)
     b.key_idx = ki.ctypes.data_as(_u32p)
-    b.a_enc, b.mta = arr(a_encs, 2 * NL), arr(mta_outs, 2 * NL)
-    b.z, b.t, b.s = (arr([getattr(p, f) for p in inner], NL) for f in ("z", "t", "s"))
+    b.a_enc, b.mta = arr(a_encs, 2 * nl), arr(mta_outs, 2 * nl)
+    b.z, b.t, b.s = (arr([getattr(p, f) for p in inner], nl) for f in ("z", "t", "s"))
     b.e, b.s1 = arr(pp["e"], b.el), arr(pp["s1"], b.s1l)
     b.s2, b.t1, b.t2 = arr(s2, b.s2l), arr(t1, b.t1l), arr(t2, b.t2l)
     if pp["ext"]:
@@ -123,10 +138,12 @@ def verify_bob(proofs, a_encs, mta_outs, eks, statements, X=None, ctx=None, fuse
 
     Raises batch.UnsupportedInput for what the C ABI does not represent: a
     negative field; an even, zero or negative N or N~ (the verifier's own keys);
-    a hashed value wider than its field (N, N~, h1, h2, z, t, s above 2048 bits,
-    a_enc, mta_out above 4096 bits).  The reference's own outcome for these
-    (a panic in mod_pow for a negative exponent, a plain rejection otherwise) is
-    not reproduced per instance.  2048-bit keys.
+    a key above 3072 bits; a hashed value wider than its field in the call's width
+    class (the smallest of 2048 and 3072 bits that fits every N and N~: h1, h2, z,
+    t, s above that width, a_enc, mta_out above twice it).  The reference's own
+    outcome for these (a panic in mod_pow for a negative exponent, a plain
+    rejection otherwise) is not reproduced per instance.  Narrower keys in a call
+    of the 3072-bit class are zero-extended; the hash covers the values as given.
 
     fused=False runs the mod-N^2 part as three separate chains (A/B timing)."""
     pp = prepass(proofs, a_encs, mta_outs, eks, statements, X)
@@ -166,13 +183,14 @@ def generate_bob(items, rng, ctx=None, check=False):
     Per proof the draws go through `rng` (sample_below) in the reference's order:
     alpha, beta (from_modulo), gamma, ro, ro_prim, sigma, tau (:266-272).  The
     exponentiations of all proofs are batched per round; every one with a secret
-    exponent runs through the regular-access kernel.  Returns BobProofs, or
-    BobProofExts with check=True."""
+    exponent runs through the regular-access kernel, at the width class of the
+    call's keys (width_class).  Returns BobProofs, or BobProofExts with check=True."""
     ctx = _ctx(ctx)
     items = list(items)
     n = len(items)
     if n == 0:
         return []
+    nl = width_class([it[4] for it in items], [it[5] for it in items])
     rnd = []
     for a_enc, mta, b, beta_prim, ek, st, r in items:
         alpha = rng.sample_below(Q3)
@@ -200,11 +218,11 @@ def generate_bob(items, rng, ctx=None, check=False):
             bases.append(base % st.N)
             exps.append(ex)
             idx.append(nt_row[st.N])
-    pw = ctx.modexp_batch(bases, exps, nts, idx, NL, secret=True)
+    pw = ctx.modexp_batch(bases, exps, nts, idx, nl, secret=True)
     va = ctx.modexp_batch([it[0] % it[4].nn for it in items], [x[0] for x in rnd], nns,
-                          [nn_row[it[4].nn] for it in items], 2 * NL, secret=True)
+                          [nn_row[it[4].nn] for it in items], 2 * nl, secret=True)
     bn = ctx.modexp_batch([x[1] for x in rnd], [it[4].n for it in items], nns, [nn_row[it[4].nn] for it in items],
-                          2 * NL)   # beta^N: public exponent
+                          2 * nl)   # beta^N: public exponent
     pts = None
     if check:   # X = G*b, u = G*alpha (:480-484)
         g = (GX, GY)
@@ -224,7 +242,7 @@ def generate_bob(items, rng, ctx=None, check=False):
         if it[4].n not in n_row:
             n_row[it[4].n] = len(ns)
             ns.append(it[4].n)
-    re = ctx.modexp_batch([it[6] % it[4].n for it in items], es, ns, [n_row[it[4].n] for it in items], NL)   # public e
+    re = ctx.modexp_batch([it[6] % it[4].n for it in items], es, ns, [n_row[it[4].n] for it in items], nl)   # public e
     out = []
     for k, ((a_enc, mta, b, beta_prim, ek, st, r), x) in enumerate(zip(items, rnd)):
         alpha, beta, gamma, ro, ro_prim, sigma, tau = x

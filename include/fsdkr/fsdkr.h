@@ -326,11 +326,26 @@ int fsdkr_modexp_joint3_batch(fsdkr_ctx* ctx, uint32_t count, const uint32_t* ba
                               const uint32_t* mod_idx, const uint32_t* mods, const uint32_t* mod_exp,
                               uint32_t exp_limbs, uint32_t n_mod, uint32_t* out);
 
+/* fsdkr_modexp_joint3_batch for moduli of k32 limbs, k32 = 128 (4096 bits) or 192
+ * (6144 bits: N^2 of the 3072-bit keys BobProof::verify, range_proofs.rs:360-446,
+ * runs at nl = 96); base, base2, base3, mods and out have k32 limbs per row.  At
+ * 192 limbs the chain runs 8 lanes per instance: a context forced to another lane
+ * count (fsdkr_ctx_set_modexp_group) gets FSDKR_E_ARG.  Any other k32:
+ * FSDKR_E_UNSUPPORTED.  fsdkr_modexp_joint3_batch is this entry at k32 = 128. */
+int fsdkr_modexp_joint3_batch_k(fsdkr_ctx* ctx, uint32_t k32, uint32_t count, const uint32_t* base,
+                                const uint32_t* base2, const uint32_t* exp2, uint32_t exp2_limbs, const uint32_t* base3,
+                                const uint32_t* exp3, const uint32_t* mod_idx, const uint32_t* mods,
+                                const uint32_t* mod_exp, uint32_t exp_limbs, uint32_t n_mod, uint32_t* out);
+
 /* ---- Bob's MtA range proofs ------------------------------------------------
  * BobProof::verify (range_proofs.rs:360-446) and BobProofExt::verify (:527-562)
  * of `count` independent proofs in one device pass.  Little-endian u32 limbs,
  * non-negative values.  The verifier's keys are a table of n_keys rows (N odd,
- * Ntilde odd, nl = 64 limbs); key_idx[p] names the row of proof p.  Values at or
+ * Ntilde odd, nl limbs); key_idx[p] names the row of proof p.  nl is the batch's
+ * width class: 64 (keys of up to 2048 bits) or 96 (up to 3072 bits), one per batch;
+ * a narrower key is zero-extended (the hash covers values without leading zeros);
+ * any other nl returns FSDKR_E_UNSUPPORTED.  At nl = 96 a context forced to a lane
+ * count other than 8 (fsdkr_ctx_set_modexp_group) gets FSDKR_E_ARG.  Values at or
  * above their modulus are reduced for the arithmetic and hashed as given.  t1 may
  * be wider than N (the honest t1 is): 1 + t1 N is taken modulo N^2.
  * X / u: affine secp256k1 points, 16 limbs (x | y), all zero = the point at
