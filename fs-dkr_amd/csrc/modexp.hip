@@ -524,11 +524,12 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_slide_kernel(const ModexpArgs
 //   (a0,a1) (b0,b1) / R = (t, h),  (t, M) = red(a0 b0),  h = red(a0 b1 + a1 b0 + M)
 // (a0 b0 = t R - M N', and N' u / R mod N'^2 depends on u / R mod N' only).  Both
 // groups stream a0 from LDS and run the same rows (Mont29::product_pair):
-//   squaring       one pass:  A: b = x0, B: b = 2 x1, coupled (lane 8 takes M's digits)
-//   times (y0,y1)  pass 1 streams y0:     A: b = x0, B: b = x1, coupled
-//                  pass 2 streams old x0: B: b = y1 (A's result unused); x1 = h1 + h2
-// so a squaring is 72 rows of 18 MACs against 144 rows of 14 in the full-width
-// chain.  x0 stays < N' (1 + 2^-6) + 2 and x1 below twice that (R >= 2^11 N').
+//   squaring       streams x0:  A: b = x0, B: b = 2 x1 (lane 8 takes M's digits)
+//   times (y0,y1)  streams y0 and the old x0 in the same rows (product_pair2):
+//                  A: y0_i x0, B: y0_i x1 + x0_i y1
+// so a squaring is 72 rows of 18 MACs and a table product 72 rows of 27, against
+// 144 rows of 14 / 18 in the full-width chain.  x0 and x1 stay < N' (1 + 2^-6) + 2
+// (R >= 2^11 N').
 // The schedule is modexp_slide_kernel's head: wave-uniform sliding windows of
 // kNadicWindow bits over the exponent bits >= lo_bit.  The raw pair goes to
 // state; the tail (modexp_tail_kernel NA) brings it into its full-width form.
@@ -588,31 +589,55 @@ __global__ __launch_bounds__(BLOCK) void modexp_nadic_head_kernel(const ModexpAr
     for (int j = 0; j < L; ++j) row[g * L + j] = acc[j];
   };
   const bool none = top < lo;   // no bits for the head: the pair of 1 (Montgomery form)
-  // phase 0: x = (base, 0) M(R);  1: x^2;  2: T[jt] = T[jt-1] x^2;  3: the windows
-  int phase = 0, i = top, pend_mul = -1;
-  uint32_t jt = 1, pend_sq = 0;
-  for (;;) {
-    if (phase == 3) {
-      if (pend_sq == 0 && pend_mul < 0)
-        while (i >= lo && !bit(i)) {
-          ++pend_sq;
-          --i;
-        }
-      for (; pend_sq; --pend_sq) {   // the squarings between two products, in a loop of their own
-        __builtin_amdgcn_wave_barrier();
-        lds_put<KD, G>(stream, acc, g);
-        __builtin_amdgcn_wave_barrier();
-        uint32_t b[L];
+  {   // x = (base, 0) M(R)
+    uint32_t b[L];
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int j = 0; j < L; ++j) b[j] = acc[j] << sh_hi;
-        M.product_pair<true>(acc, b, stream);
-      }
+    for (int j = 0; j < L; ++j) {
+      const int d = g * L + j;
+      b[j] = C[kNadicR0 + d];   // r in group A, (N' - q) in group B
+      if (!hi) stream[d] = none ? (d == 0 ? 1u : 0u) : digit_of(B, blen, d);
     }
-    const uint32_t* src = nullptr;
-    if (phase == 2) {
-      src = T + (size_t)tw * KD;
-    } else if (phase == 3) {
-      if (pend_mul >= 0) {
+    __builtin_amdgcn_wave_barrier();
+    M.product_pair(acc, b, stream);
+  }
+  // the squarings: A: b = x0, B: b = 2 x1
+  auto square = [&]() {
+    __builtin_amdgcn_wave_barrier();
+    lds_put<KD, G>(stream, acc, g);
+    __builtin_amdgcn_wave_barrier();
+    uint32_t b[L];
+#pragma unroll
+    for (int j = 0; j < L; ++j) b[j] = acc[j] << sh_hi;
+    M.product_pair(acc, b, stream);
+  };
+  if (!none) {
+    store(T);
+    square();
+    store(T + (size_t)tw * KD);   // x^2
+    load(T);
+    // phase 2: T[jt] = T[jt-1] x^2;  3: the windows
+    int phase = tw > 1 ? 2 : 3, i = top, pend_mul = -1;
+    uint32_t jt = 1, pend_sq = 0;
+    for (;;) {
+      if (phase == 3) {
+        if (i == top) {   // the first window: its odd power, no squarings of 1
+          int jl;
+          const uint32_t d = window(i, &jl);
+          load(T + (size_t)(d >> 1) * KD);
+          i = jl - 1;
+        }
+        if (pend_sq == 0 && pend_mul < 0)
+          while (i >= lo && !bit(i)) {
+            ++pend_sq;
+            --i;
+          }
+        for (; pend_sq; --pend_sq) square();   // the squarings between two products, in a loop of their own
+      }
+      const uint32_t* src;
+      if (phase == 2) {
+        src = T + (size_t)tw * KD;
+      } else if (pend_mul >= 0) {
         src = T + (size_t)pend_mul * KD;
         pend_mul = -1;
       } else if (i < lo) {
@@ -625,64 +650,26 @@ __global__ __launch_bounds__(BLOCK) void modexp_nadic_head_kernel(const ModexpAr
         i = jl - 1;
         continue;
       }
-    }
-    // one coupled pass: the entry product, x^2, or pass 1 of a table product
-    uint32_t b[L], y[L];
-    __builtin_amdgcn_wave_barrier();
-    if (phase == 0) {
+      // the table product, one coupled pass: A: y0 x0, B: y0 x1 + x0 y1 + M
+      uint32_t y[L];
+      __builtin_amdgcn_wave_barrier();
 #pragma unroll
-      for (int j = 0; j < L; ++j) {
-        const int d = g * L + j;
-        b[j] = C[kNadicR0 + d];   // r in group A, (N' - q) in group B
-        if (!hi) stream[d] = none ? (d == 0 ? 1u : 0u) : digit_of(B, blen, d);
-      }
-    } else if (phase == 1) {
-      lds_put<KD, G>(stream, acc, g);
-#pragma unroll
-      for (int j = 0; j < L; ++j) b[j] = acc[j] << sh_hi;
-    } else {
-#pragma unroll
-      for (int j = 0; j < L; ++j) {
-        y[j] = src[g * L + j];
-        b[j] = acc[j];
-      }
-      if (!hi) {   // y0 for pass 1, the old x0 for pass 2
+      for (int j = 0; j < L; ++j) y[j] = src[g * L + j];
+      if (!hi) {   // the two streamed operands: y0 and the old x0
 #pragma unroll
         for (int j = 0; j < L; ++j) {
           stream[g * L + j] = y[j];
           stream[72 + g * L + j] = acc[j];
         }
       }
-    }
-    __builtin_amdgcn_wave_barrier();
-    M.product_pair<true>(b, b, stream);
-    if (src) {   // pass 2: B: old x0 * y1, uncoupled (A's operand only has to be bounded)
 #pragma unroll
-      for (int j = 0; j < L; ++j) y[j] = hi ? y[j] : acc[j];
-      M.product_pair<false>(y, y, stream + 72);
-#pragma unroll
-      for (int j = 0; j < L; ++j) acc[j] = b[j] + (y[j] & m_hi);
-    } else {
-#pragma unroll
-      for (int j = 0; j < L; ++j) acc[j] = b[j];
-    }
-    if (phase == 0) {
-      if (none) break;
-      store(T);
-      phase = 1;
-    } else if (phase == 1) {
-      store(T + (size_t)tw * KD);
-      load(T);
-      phase = tw > 1 ? 2 : 3;
-    } else if (phase == 2) {
-      store(T + (size_t)jt * KD);
-      if (++jt == tw) phase = 3;
-    }
-    if (phase == 3 && i == top) {   // the first window: its odd power, no squarings of 1
-      int jl;
-      const uint32_t d = window(i, &jl);
-      load(T + (size_t)(d >> 1) * KD);
-      i = jl - 1;
+      for (int j = 0; j < L; ++j) y[j] &= m_hi;   // A: 0, B: y1
+      __builtin_amdgcn_wave_barrier();
+      M.product_pair2(acc, acc, y, stream, stream + 72);
+      if (phase == 2) {
+        store(T + (size_t)jt * KD);
+        if (++jt == tw) phase = 3;
+      }
     }
   }
 #pragma unroll

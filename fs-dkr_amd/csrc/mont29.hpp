@@ -448,14 +448,20 @@ struct Mont29 {
   // ---- coupled pair of 8-lane groups (the N-adic product of modexp.hip) ----------
   // Two groups share one 16-lane DPP row: group A (lanes 0-7) and group B (lanes
   // 8-15) stream the SAME operand a and run the same quotient-scaled plain rows,
-  // each on its own register operand b.  With CPL the rows are coupled: lane 8
-  // adds group A's quotient digit m_i (row_newbcast:0 already puts it in all 16
-  // lanes) to its retiring column before group B's own quotient digit is taken,
-  // so with red(T) = (t, M), T + M N' = t R, the pass computes
+  // each on its own register operand b.  The rows are coupled: lane 8 adds group
+  // A's quotient digit m_i (row_newbcast:0 already puts it in all 16 lanes) to its
+  // retiring column before group B's own quotient digit is taken, so with
+  // red(T) = (t, M), T + M N' = t R, the pass computes
   //   A: (t, M) = red(a bA)      B: h = red(a bB + M).
-  // Digits of bB may be doubled and summed ones (<= 2^31 + 508): a column gains
-  // < 9 (2^60.01 + 2^58) + 2^29 + 2^35 < 2^63.6 over its stay
-  // (tests/test_nadic_model.py).  pair_one: 1 in lane 8 of the row, else 0.
+  // TWO: a second streamed operand a2 with its own register operand b2 rides the
+  // same rows, acc += a_i b + a2_i b2:
+  //   A: (t, M) = red(a bA + a2 b2A)      B: h = red(a bB + a2 b2B + M)
+  // (the table product of the N-adic head in one pass, b2A = 0).
+  // One streamed operand: digits of bB may be doubled ones (<= 2^30 + 254), a
+  // column gains < 9 (2^59.01 + 2^58) + 2^29 + 2^35 < 2^62.8 over its stay.  Two:
+  // all digits <= 2^29 + 127, < 9 (2 2^58.01 + 2^58) + 2^29 + 2^35 < 2^62.8
+  // (tests/test_nadic_model.py, tests/test_nadic_onepass_model.py).
+  // pair_one: 1 in lane 8 of the row, else 0.
   uint32_t pair_one;
   __device__ __forceinline__ void init_pair(int lane16) {
     static_assert(G == 8, "a pair of 8-lane groups in one DPP row");
@@ -463,48 +469,66 @@ struct Mont29 {
     pair_one = (lane16 == 8) ? 1u : 0u;
     asm volatile("" : "+v"(pair_one));
   }
-  template <int R, bool CPL>
-  __device__ __forceinline__ void row_pair(uint64_t* acc, const uint32_t* b, const uint32_t* n, uint32_t ai) const {
+  template <int R, bool TWO>
+  __device__ __forceinline__ void row_pair(uint64_t* acc, const uint32_t* b, const uint32_t* b2, const uint32_t* n,
+                                           uint32_t ai, uint32_t a2i) const {
     constexpr int s0 = R % L, s1 = (R + 1) % L;
 #pragma unroll
     for (int j = 0; j < L; ++j) mac(acc[(j + R) % L], ai, b[j]);
-    uint32_t m;
-    if constexpr (CPL) {
-      const uint32_t ma = FSDKR_DPP((uint32_t)acc[s0], 0x150) & m29;   // group A's quotient digit, all 16 lanes
-      mac(acc[s0], ma, pair_one);                                       // lane 8: + m_i
-      m = FSDKR_DPP_BANK(ma, (uint32_t)acc[s0], 0x158, 0xC) & m29;      // lanes 8-15: group B's own
-    } else {
-      m = bcast_lane0<G>((uint32_t)acc[s0]) & m29;
+    if constexpr (TWO) {
+#pragma unroll
+      for (int j = 0; j < L; ++j) mac(acc[(j + R) % L], a2i, b2[j]);
     }
+    const uint32_t ma = FSDKR_DPP((uint32_t)acc[s0], 0x150) & m29;                  // group A's quotient digit, all 16 lanes
+    mac(acc[s0], ma, pair_one);                                                      // lane 8: + m_i
+    const uint32_t m = FSDKR_DPP_BANK(ma, (uint32_t)acc[s0], 0x158, 0xC) & m29;      // lanes 8-15: group B's own
 #pragma unroll
     for (int j = 0; j < L; ++j) mac(acc[(j + R) % L], m, n[j]);
     acc[s1] += acc[s0] >> 29;
     acc[s0] = (uint64_t)(dpp_next<G>((uint32_t)acc[s0]) & m_top29);
   }
-  template <bool CPL, int... Rs>
-  __device__ __forceinline__ void cycle_pair(uint64_t* acc, const uint32_t* b, const uint32_t* n, const uint32_t* arow,
-                                             uint32_t carried, std::integer_sequence<int, Rs...>) const {
-    (row_pair<Rs, CPL>(acc, b, n, Rs == 0 ? carried : arow[Rs]), ...);
+  template <bool TWO, int... Rs>
+  __device__ __forceinline__ void cycle_pair(uint64_t* acc, const uint32_t* b, const uint32_t* b2, const uint32_t* n,
+                                             const uint32_t* arow, const uint32_t* arow2, uint32_t carried,
+                                             uint32_t carried2, std::integer_sequence<int, Rs...>) const {
+    (row_pair<Rs, TWO>(acc, b, b2, n, Rs == 0 ? carried : arow[Rs], !TWO ? 0u : Rs == 0 ? carried2 : arow2[Rs]), ...);
   }
-  // out = the pass above for this lane's group; a_lds: the KD streamed digits.
-  // out may alias b.
-  template <bool CPL>
-  __device__ __forceinline__ void product_pair(uint32_t* out, uint32_t* b, const uint32_t* a_lds) {
+  // out = the pass above for this lane's group; a_lds (and a2_lds): the KD streamed
+  // digits.  out may alias b.
+  template <bool TWO>
+  __device__ __forceinline__ void product_pair_impl(uint32_t* out, uint32_t* b, uint32_t* b2, const uint32_t* a_lds,
+                                                    const uint32_t* a2_lds) {
     static_assert(G == 8 && L <= 12, "a pair of short-lane 8-lane groups");
     uint64_t acc[L];
 #pragma unroll
     for (int j = 0; j < L; ++j) acc[j] = 0;
     uint32_t car = a_lds[0];   // the next cycle's first digit, read a cycle ahead (product())
+    uint32_t car2 = TWO ? a2_lds[0] : 0u;
 #pragma unroll 1
     for (int cyc = 0; cyc < G; ++cyc) {
       uint32_t nx = a_lds[(cyc + 1 < G ? cyc + 1 : 0) * L];
+      uint32_t nx2 = TWO ? a2_lds[(cyc + 1 < G ? cyc + 1 : 0) * L] : 0u;
       opaque<L>(b);
+      if constexpr (TWO) opaque<L>(b2);
       opaque<L>(n);
-      cycle_pair<CPL>(acc, b, n, a_lds + cyc * L, car, std::make_integer_sequence<int, L>{});
+      cycle_pair<TWO>(acc, b, b2, n, a_lds + cyc * L, TWO ? a2_lds + cyc * L : nullptr, car, car2,
+                      std::make_integer_sequence<int, L>{});
       asm volatile("" : "+v"(nx));
       car = nx;
+      if constexpr (TWO) {
+        asm volatile("" : "+v"(nx2));
+        car2 = nx2;
+      }
     }
     finish(out, acc);
+  }
+  __device__ __forceinline__ void product_pair(uint32_t* out, uint32_t* b, const uint32_t* a_lds) {
+    product_pair_impl<false>(out, b, nullptr, a_lds, nullptr);
+  }
+  // the pass with two streamed operands: out may alias b or b2
+  __device__ __forceinline__ void product_pair2(uint32_t* out, uint32_t* b, uint32_t* b2, const uint32_t* a_lds,
+                                                const uint32_t* a2_lds) {
+    product_pair_impl<true>(out, b, b2, a_lds, a2_lds);
   }
 
   // G = 64 (one instance per wave): the streamed operand is held in registers
