@@ -160,6 +160,28 @@ struct EcMsmArgs {          // out[o] = sum_j scalars[o][j] * P[o][j]
   uint32_t prio;            // s_setprio level (0..3)
 };
 
+// Secret-scalar secp256k1 (ec_ct.hip).  The launches cover whole waves and the
+// kernels check no bound, so every array is padded to count_pad entries.
+constexpr uint32_t kEcMulGPad = 16;    // scalars per wave (four lanes each)
+constexpr uint32_t kEcMsmCtPad = 64;   // outputs per wave
+constexpr uint32_t kEcCombEntries = 64 * 16 + 1;   // T[i][d] = (d + 1) 16^i G, then -C
+
+struct EcMulGCtArgs {       // out[i] = scalars[i] * G
+  const uint32_t* table;    // [kEcCombEntries][16] affine
+  const uint32_t* scalars;  // [count_pad][8]
+  uint32_t* out;            // [count_pad][16] affine
+  uint32_t count_pad;       // a multiple of kEcMulGPad
+};
+
+struct EcMsmCtArgs {        // out[o] = sum_j scalars[o][j] * points[o][j]
+  const uint32_t* points;   // [count_pad][terms][16] affine, (0, 0) = infinity
+  const uint32_t* scalars;  // [count_pad][terms][8]
+  uint32_t terms;
+  uint32_t* out;            // [count_pad][16] affine
+  uint32_t count_pad;       // a multiple of kEcMsmCtPad
+  uint32_t* scratch;        // [count_pad][terms][24] projective terms (EcMsmArgs' layout)
+};
+
 hipError_t launch_binom(const BinomArgs& a, hipStream_t st);
 hipError_t launch_ped_hash(const PedHashArgs& a, hipStream_t st);
 hipError_t launch_alice_hash(const AliceHashArgs& a, hipStream_t st);
@@ -180,6 +202,8 @@ hipError_t launch_prod3(uint32_t k32, const Prod3Args& a, hipStream_t st);
 hipError_t launch_pdl_u1(const PdlU1Args& a, hipStream_t st);
 hipError_t launch_feldman(const FeldmanArgs& a, hipStream_t st);
 hipError_t launch_ec_msm(const EcMsmArgs& a, hipStream_t st);
+hipError_t launch_ec_mul_g_ct(const EcMulGCtArgs& a, hipStream_t st);
+hipError_t launch_ec_msm_ct(const EcMsmCtArgs& a, hipStream_t st);
 hipError_t launch_pow2_check(const Pow2Args& a, hipStream_t st);
 
 }  // namespace fsdkr

@@ -212,6 +212,10 @@ def lib():
     L.fsdkr_miller_rabin.restype = ctypes.c_int
     L.fsdkr_ec_msm.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p]
     L.fsdkr_ec_msm.restype = ctypes.c_int
+    L.fsdkr_ec_msm_ct.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p]
+    L.fsdkr_ec_msm_ct.restype = ctypes.c_int
+    L.fsdkr_ec_mul_g_ct.argtypes = [vp, ctypes.c_uint32, u32p, u32p]
+    L.fsdkr_ec_mul_g_ct.restype = ctypes.c_int
     L.fsdkr_fixed_base_modexp.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p, ctypes.c_uint32,
                                           ctypes.c_uint32, u32p, u32p, ctypes.c_uint32, u32p]
     L.fsdkr_fixed_base_modexp.restype = ctypes.c_int
@@ -718,17 +722,39 @@ class Context:
             at += n
         return res
 
-    def ec_msm(self, points, scalars):
-        """points/scalars: lists (count) of equal-length lists; points are (x, y) or None."""
+    def ec_msm(self, points, scalars, secret=False):
+        """points/scalars: lists (count) of equal-length lists; points are (x, y) or None.
+        secret=True: the scalars are secret (fsdkr_ec_msm_ct: no scalar-dependent
+        address or branch); the results are the same points."""
         from . import _pack
-        count, terms = len(points), len(points[0])
+        count = len(points)
+        if count == 0:
+            return []
+        terms = len(points[0])
         Pt = np.empty((count * terms, 16), dtype=np.uint32)
         _pack.points([pt for row in points for pt in row], None, Pt)
         Sc = ints_to_limbs([s for row in scalars for s in row], 8)
         O = np.zeros((count, 16), dtype=np.uint32)
-        self.check(self._lib.fsdkr_ec_msm(self._h, count, terms, _ptr(Pt), _ptr(Sc), _ptr(O)))
-        out = []
-        for v in limbs_to_ints(O):
-            x, y = v & ((1 << 256) - 1), v >> 256
-            out.append(None if (x == 0 and y == 0) else (x, y))
-        return out
+        fn = self._lib.fsdkr_ec_msm_ct if secret else self._lib.fsdkr_ec_msm
+        self.check(fn(self._h, count, terms, _ptr(Pt), _ptr(Sc), _ptr(O)))
+        return _points_out(O)
+
+    def ec_mul_g(self, scalars):
+        """[k * G for k in scalars] for SECRET scalars (0 <= k < 2^256), always through
+        the constant-time entry fsdkr_ec_mul_g_ct; points are (x, y) or None."""
+        count = len(scalars)
+        if count == 0:
+            return []
+        Sc = ints_to_limbs(list(scalars), 8)
+        O = np.zeros((count, 16), dtype=np.uint32)
+        self.check(self._lib.fsdkr_ec_mul_g_ct(self._h, count, _ptr(Sc), _ptr(O)))
+        return _points_out(O)
+
+
+def _points_out(O):
+    """[count][16] affine limbs -> (x, y) tuples, None for the ABI's infinity (0, 0)."""
+    out = []
+    for v in limbs_to_ints(O):
+        x, y = v & ((1 << 256) - 1), v >> 256
+        out.append(None if (x == 0 and y == 0) else (x, y))
+    return out

@@ -5,14 +5,15 @@ job 1 (Paillier encryption of the new shares, :72-84).
 Every exponentiation runs on the GPU in a few batched launches:
   round 1  job-1 encryptions (fsdkr_paillier_encrypt); the PDL / Alice
            commitments h1^x h2^rho, h1^alpha h2^gamma mod N~ and beta^N mod N^2
-           (fsdkr_modexp_batch); G*share, G*a_k, G*alpha (fsdkr_ec_msm)
+           (fsdkr_modexp_batch); G*share, G*a_k, G*alpha (fsdkr_ec_mul_g_ct)
   round 2  r^e mod N for the PDL s2 and Alice s responses (after the challenges)
   keys     Paillier / ring-Pedersen moduli by the batched GPU Miller-Rabin prime
            walk (fsdkr/keygen.py), correct-key sigma_j = rho_j^(N^-1 mod phi),
            ring-Pedersen A_i = T^a_i.
 Every exponentiation with a secret exponent (alpha, gamma, rho, the share x,
 a_i, lambda, xhi, N^-1 mod phi, the DLog proof's r) runs through the
-regular-access kernel (fsdkr_modexp_batch_ct: no exponent-dependent addresses).
+regular-access kernel (fsdkr_modexp_batch_ct: no exponent-dependent addresses),
+and every multiplication of G by a secret scalar through fsdkr_ec_mul_g_ct.
 Hashes, small-number arithmetic and the order of random draws are host work.
 
 Randomness is injected: `rng` provides sample_below(n) and bits(k) (the
@@ -192,9 +193,8 @@ def distribute(old_party_index, local_key, new_n, rng=None, ctx=None, key_bits=2
                           [eks[i].n for i in range(n)] * 2, [eks[i].nn for i in range(n)] * 2,
                           list(range(2 * n)), 2 * wN)
     G = (GX, GY)
-    pts = [[G] for _ in range(n + len(coeffs) + n)]
-    scs = [[s] for s in shares] + [[c] for c in coeffs] + [[pd[i]["alpha"] % Q] for i in range(n)]
-    ecr = ctx.ec_msm(pts, scs)
+    # secret scalars (the shares, the polynomial, the PDL blinding): the constant-time comb
+    ecr = ctx.ec_mul_g(list(shares) + list(coeffs) + [pd[i]["alpha"] % Q for i in range(n)])
     committed, comms, u1s = ecr[:n], ecr[n:n + len(coeffs)], ecr[n + len(coeffs):]
     # ---- challenges (host), round 2 on the GPU
     e_pdl, e_al = [], []

@@ -11,7 +11,7 @@ CPU fallback."""
 import secrets
 
 from .batch import UnsupportedInput
-from .refresh import GX, GY, Q, FsDkrError, FsDkrPanic, _ctx, recover_share
+from .refresh import Q, FsDkrError, FsDkrPanic, _ctx, recover_share
 from .types import DLogStatement, EncryptionKey, LocalKey, VerifiableSS
 
 
@@ -82,12 +82,13 @@ def verify_ring_pedersen(ctx, messages, m_security=256):
 def vss_share(ctx, t, n, secret, sample_below=None):
     """VerifiableSS::share(t, n, secret) commitments (curv feldman_vss [dep]): a
     random degree-t polynomial with constant term `secret` and a non-zero top
-    coefficient; commitments G*a_k via one GPU MSM launch."""
+    coefficient; commitments G*a_k via one launch of the constant-time comb
+    (the coefficients are secret: fsdkr_ec_mul_g_ct)."""
     draw = sample_below or secrets.randbelow
     coeffs = [secret % Q] + [draw(Q) for _ in range(t)]
     while t > 0 and coeffs[-1] == 0:
         coeffs[-1] = draw(Q)
-    com = ctx.ec_msm([[(GX, GY)] for _ in coeffs], [[a] for a in coeffs])
+    com = ctx.ec_mul_g(coeffs)
     return VerifiableSS(threshold=t, share_count=n, commitments=com)
 
 

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _native
 from .batch import UnsupportedInput, _limbs_for, pack, pack_points
-from .refresh import GX, GY, Q, FsDkrPanic, _ctx
+from .refresh import Q, FsDkrPanic, _ctx
 from .types import BobProof, BobProofExt
 
 PANIC = 2          # verdict: the reference panics (X or u at infinity, range_proofs.rs:428-431)
@@ -224,9 +224,8 @@ def generate_bob(items, rng, ctx=None, check=False):
     bn = ctx.modexp_batch([x[1] for x in rnd], [it[4].n for it in items], nns, [nn_row[it[4].nn] for it in items],
                           2 * nl)   # beta^N: public exponent
     pts = None
-    if check:   # X = G*b, u = G*alpha (:480-484)
-        g = (GX, GY)
-        pts = ctx.ec_msm([[g] for _ in range(2 * n)], [[it[2] % Q] for it in items] + [[x[0] % Q] for x in rnd])
+    if check:   # X = G*b, u = G*alpha (:480-484): secret scalars, the constant-time comb
+        pts = ctx.ec_mul_g([it[2] % Q for it in items] + [x[0] % Q for x in rnd])
     es, firsts = [], []
     for k, ((a_enc, mta, b, beta_prim, ek, st, r), x) in enumerate(zip(items, rnd)):
         p = pw[8 * k:8 * k + 8]

@@ -6,6 +6,7 @@ ring_pedersen_proof.rs:48-124, add_party_message.rs:50-124).
 Every exponentiation (prime tests, encryptions, commitments, proof responses,
 ring-Pedersen A_i, correct-key sigma_j, composite-DLog x) runs through
 Context.modexp_batch; every scalar multiplication through Context.ec_msm.
+(It keeps the public-scalar ec_msm: the data is synthetic, not a prover's secrets.)
 Randomness is a seeded PRNG (synthetic data, not a production prover); the
 statistical shapes follow the reference's samplers."""
 import hashlib

@@ -550,6 +550,34 @@ int fsdkr_paillier_decrypt_multi(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, co
 int fsdkr_ec_msm(fsdkr_ctx* ctx, uint32_t count, uint32_t terms, const uint32_t* points, const uint32_t* scalars,
                  uint32_t* out);
 
+/* ---- secp256k1 scalar multiplication for SECRET scalars ---------------------
+ * out[i] = scalars[i] * G for SECRET scalars (8 limbs, any value < 2^256; no
+ * reduction mod q is needed), affine 16-limb results, (0, 0) for the point at
+ * infinity: the prover's G*share, G*a_k (Feldman coefficients), the PDL
+ * blinding G*alpha and Bob's X = G*b, u = G*alpha.  The kernel's memory
+ * addresses and instruction stream do not depend on the scalar: a comb over a
+ * table of (d + 1) 16^i G without a zero digit, every window's 16 entries read
+ * and one kept through a mask, complete projective additions (Renes, Costello,
+ * Batina 2016) with masked field reductions, no branch on data.
+ *
+ * Replaces curv `Point::generator() * Scalar` (libsecp256k1's constant-time
+ * secp256k1_ecmult_gen behind it) as called from refresh_message.rs:51-145,
+ * zk_pdl_with_slack.rs:53-111 and range_proofs.rs:480-484.  The device buffers
+ * that held the scalars are zeroed before the call returns; the host arrays
+ * are the caller's.  Runs on the context's recovery stream like fsdkr_ec_msm. */
+int fsdkr_ec_mul_g_ct(fsdkr_ctx* ctx, uint32_t count, const uint32_t* scalars, uint32_t* out);
+
+/* fsdkr_ec_msm for SECRET scalars: identical results, but the kernels' memory
+ * addresses and instruction stream do not depend on the scalars.  Every term
+ * runs 64 fixed 4-bit windows (four complete doublings and one complete
+ * addition each, no GLV split) over a 16-entry table of its point, scanned
+ * whole through a mask per window; a point at infinity takes the same path.
+ * Points are public; the per-term products and the scalars are zeroed on the
+ * device before the call returns.  For terms whose point is G use
+ * fsdkr_ec_mul_g_ct, which is several times shorter. */
+int fsdkr_ec_msm_ct(fsdkr_ctx* ctx, uint32_t count, uint32_t terms, const uint32_t* points,
+                    const uint32_t* scalars, uint32_t* out);
+
 /* Share recovery of collect() in one call, for `count` independent jobs (one
  * party of RefreshMessage::collect, JoinMessage::collect, or one session of a
  * multi-session batch): refresh_message.rs:367-373 (get_ciphertext_sum) and
