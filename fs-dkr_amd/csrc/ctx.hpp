@@ -177,6 +177,7 @@ struct ModexpJob {
 };
 
 uint32_t choose_window(uint32_t ebits);
+uint32_t choose_slide_window(uint32_t ebits);   // the sliding-window launches' width for an exponent of ebits bits
 // launch_modexp_desc desc_flags: the descriptors end with out_idx (ModexpJob.out_idx);
 // the instances of every wave share their exponent (sliding windows)
 constexpr uint32_t kDescOutIdx = 1, kDescSlide = 2;

@@ -17,13 +17,6 @@
 
 namespace fsdkr {
 
-template <int KD, int G>
-__device__ __forceinline__ void lds_put(uint32_t* stream, const uint32_t* d, int g) {
-  constexpr int L = KD / G;
-#pragma unroll
-  for (int j = 0; j < L; ++j) stream[g * L + j] = d[j];
-}
-
 // consts row m (cons_stride(KD) words, kernels.h) = {N digits | R mod N | R^2 mod N |
 // ninv}, then when scaled_ok(KD, K32) the same block for N' = N (-N^-1 mod 2^29)
 // (the quotient-scaled chains of modexp_kernel<..., QS>).  Instances m < n_mod
@@ -156,20 +149,6 @@ __global__ __launch_bounds__(64) void mod_setup_wave_kernel(const uint32_t* __re
     }
   }
   if (g == 0) out[3 * KR] = M.ninv;
-}
-
-// dst = this lane's digits of table row d, read by scanning every row and keeping
-// row d through a mask: the addresses and the instruction stream do not depend
-// on d (a secret exponent's window digit).
-template <int L>
-__device__ __forceinline__ void ct_row(uint32_t* dst, const uint32_t* T, uint32_t d, uint32_t rows, int KD, int g) {
-#pragma unroll
-  for (int j = 0; j < L; ++j) dst[j] = 0u;
-  for (uint32_t e = 0; e < rows; ++e) {
-    const uint32_t m = 0u - (uint32_t)(e == d);
-#pragma unroll
-    for (int j = 0; j < L; ++j) dst[j] |= T[(size_t)e * KD + g * L + j] & m;
-  }
 }
 
 // CT: the regular-access variant for secret exponents (a separate instantiation:

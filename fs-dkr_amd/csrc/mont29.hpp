@@ -667,4 +667,27 @@ __device__ __forceinline__ uint32_t limb_of(const uint32_t* d, int KD, int k) {
   return (uint32_t)(v >> sh);
 }
 
+// ---- helpers shared by the exponentiation kernels (modexp.hip, mta_ct.hip) ----
+// this lane's L digits into the instance's streamed LDS row
+template <int KD, int G>
+__device__ __forceinline__ void lds_put(uint32_t* stream, const uint32_t* d, int g) {
+  constexpr int L = KD / G;
+#pragma unroll
+  for (int j = 0; j < L; ++j) stream[g * L + j] = d[j];
+}
+
+// dst = this lane's digits of table row d, read by scanning every row and keeping
+// row d through a mask: the addresses and the instruction stream do not depend
+// on d (a secret exponent's window digit).
+template <int L>
+__device__ __forceinline__ void ct_row(uint32_t* dst, const uint32_t* T, uint32_t d, uint32_t rows, int KD, int g) {
+#pragma unroll
+  for (int j = 0; j < L; ++j) dst[j] = 0u;
+  for (uint32_t e = 0; e < rows; ++e) {
+    const uint32_t m = 0u - (uint32_t)(e == d);
+#pragma unroll
+    for (int j = 0; j < L; ++j) dst[j] |= T[(size_t)e * KD + g * L + j] & m;
+  }
+}
+
 }  // namespace fsdkr

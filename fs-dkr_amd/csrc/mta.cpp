@@ -4,6 +4,8 @@
 //   fsdkr_bob_verify            BobProof::verify (range_proofs.rs:360-446) and
 //                               BobProofExt::verify (:527-562), `count` proofs in one pass
 //   fsdkr_bob_verify_unfused    the same verdicts with three separate mod-N^2 chains (A/B)
+//   fsdkr_mta_respond           Bob's response a_enc^b (1 + beta' N) r^N mod N^2 (:688-704), see below
+//   fsdkr_mta_respond_unfused   the same values from separate chains and one product (A/B)
 // Per proof, in the reference's order: s1 <= q^3 (:374); z^e, mta^e, t^e units
 // (:378-406); z' = h1^s1 h2^s2 z^-e, w = h1^t1 h2^t2 t^-e mod N~ (:385-388, :408-411);
 // v = a_enc^s1 s^N (1 + t1 N) mta^-e mod N^2 (:396-400); the transcript hash
@@ -19,6 +21,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "collect.hpp"
@@ -587,6 +590,240 @@ int fsdkr_bob_verify_unfused(fsdkr_ctx* ctx, const fsdkr_bob_batch* batch, uint8
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
   if (!c) return FSDKR_E_ARG;
   return bob_verify_impl(c, "fsdkr_bob_verify_unfused", batch, verdict, false);
+}
+
+}  // extern "C"
+
+// ---- Bob's MtA response --------------------------------------------------------
+// mta_out = Paillier::add(Paillier::mul(ek, a_enc, b), Enc(beta'; r))
+//         = a_enc^b (1 + beta' N) r^N mod N^2        (range_proofs.rs:688-704)
+// with b, beta' and r secret.  Fused (nl = 64): the head of r^N over N's bits >= 256
+// (modexp_slide_kernel: r is only the base; 16, 8 or 4 lanes by batch size), then
+// the 8-lane mta_tail_ct_kernel (mta_ct.hip), which carries a_enc^b along the last
+// 256 squarings in regular access and takes 1 + beta' N as the operand of its exit
+// product.  Composed (nl = 96, or unfused): a_enc^b through the regular-access
+// modexp, r^N as fsdkr_paillier_encrypt runs it, and prod3 of the two with
+// 1 + beta' N; nothing returns to the host in between.
+namespace {
+
+void wipe(std::vector<uint32_t>& v) {
+  volatile uint32_t* p = v.data();
+  for (size_t k = 0; k < v.size(); ++k) p[k] = 0u;
+}
+
+// zero a named context buffer on the context's stream (no-op if it was never made)
+int scrub(Ctx* c, const std::string& name) {
+  const auto it = c->bufs.find(name);
+  if (it == c->bufs.end() || !it->second.ptr || !it->second.bytes) return FSDKR_OK;
+  return c->hip_check(hipMemsetAsync(it->second.ptr, 0, it->second.bytes, c->stream), "scrub");
+}
+
+int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const uint32_t* a_enc, const uint32_t* b,
+                     const uint32_t* beta_prim, const uint32_t* r, const uint32_t* n_idx, const uint32_t* ns,
+                     uint32_t nk, uint32_t* out, bool want_fused) {
+  if (nl != 64 && nl != 96) {
+    c->fail("%s: unsupported modulus width %u limbs", who, nl);
+    return FSDKR_E_UNSUPPORTED;
+  }
+  if (count == 0) return FSDKR_OK;
+  if (!a_enc || !b || !beta_prim || !r || !n_idx || !ns || !out || !nk) {
+    c->fail("%s: bad argument", who);
+    return FSDKR_E_ARG;
+  }
+  const uint32_t nn = 2 * nl;
+  const bool fused = want_fused && nl == 64;
+  if (fused && c->modexp_group != 0 && c->modexp_group != kMtaTailPad) {
+    c->fail("%s: the fused chain runs at 8 lanes (forced %u)", who, c->modexp_group);
+    return FSDKR_E_ARG;
+  }
+  std::vector<uint32_t> NN((size_t)nk * nn);
+  uint32_t nbits = 1;
+  for (uint32_t k = 0; k < nk; ++k) {
+    const uint32_t* N = ns + (size_t)k * nl;
+    if (!(N[0] & 1u) || bit_len(N, nl) < 2) {
+      c->fail("%s: key %u: N must be odd and above 1", who, k);
+      return FSDKR_E_ARG;
+    }
+    const hbn::Limbs Nv = hbn::from(N, nl);
+    hbn::store(hbn::mul(Nv, Nv), &NN[(size_t)k * nn], nn);
+    nbits = std::max(nbits, bit_len(N, nl));
+  }
+  for (uint32_t p = 0; p < count; ++p) {
+    if (n_idx[p] >= nk) {
+      c->fail("%s: n_idx[%u] out of range", who, p);
+      return FSDKR_E_ARG;
+    }
+    if (hbn::cmp_raw(a_enc + (size_t)p * nn, nn, &NN[(size_t)n_idx[p] * nn], nn) >= 0) {   // public
+      c->fail("%s: a_enc[%u] is not reduced modulo N^2", who, p);
+      return FSDKR_E_ARG;
+    }
+  }
+  const size_t C = count, rl = (size_t)nl * 4, rn = (size_t)nn * 4;
+  auto DA0 = [](size_t o) { return (uint64_t)o; };   // offsets until the buffer exists
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = al256(off + (bytes ? bytes : 1)); return o; };
+  const size_t o_N = take(nk * rl), o_NN = take(nk * rn), o_r = take(C * rl);
+  // r^N: every wave shares its exponent N.  Fused: 8 chains per wave, the pads write a
+  // scratch row; composed: as fsdkr_paillier_encrypt (the pads rewrite their own row)
+  ModexpJob J;
+  J.k32 = nn;
+  for (uint32_t p = 0; p < count; ++p)
+    J.add(DA0(o_r + p * rl), nl, DA0(o_N + n_idx[p] * rl), nl, fused ? bit_len(ns + (size_t)n_idx[p] * nl, nl) : 32 * nl,
+          n_idx[p]);
+  uint32_t G = 0, flags = 0;
+  if (fused) {
+    // state and table rows are 144 digits in order whatever the lanes, so the head
+    // picks its lanes as the keyed launches do (a batch that leaves the chip half empty
+    // at 8 lanes runs 16) unless 8 are forced; the runs of one key are padded to whole
+    // waves of both kernels: 8 chains of the tail, 16 of a 4-lane head
+    G = c->modexp_group ? kMtaTailPad : keyed_lanes(count);
+    if (!group_by_exponent(J, std::max(kMtaTailPad, 64 / G), count)) {
+      c->fail("%s: instances not wave-uniform", who);
+      return FSDKR_E_ARG;
+    }
+    flags = ga_desc_flags(true, G);
+  } else if (nn == 128) {
+    G = keyed_lanes(count);
+    if (group_by_exponent(J, 64 / G, kPadSelf)) flags = kDescOutIdx | kDescSlide;
+    else G = 0;
+  }
+  // rows of the tail's operands: launch order (fused) or the caller's (composed)
+  const size_t n = fused ? J.size() : C, n64 = (n + 63) / 64 * 64;
+  std::vector<uint32_t> row(n);   // the caller's instance behind row k; a pad repeats the chain before it
+  std::vector<uint8_t> pad(n, 0);
+  for (size_t k = 0; k < n; ++k) {
+    const uint32_t o = fused ? J.out_idx[k] : (uint32_t)k;
+    pad[k] = o >= count;
+    row[k] = pad[k] ? row[k - 1] : o;   // a run's pads follow its chains
+  }
+  const size_t o_a = take(n * rn), o_b = take(n * 32), o_bp = take(n64 * rl), o_np = take(n64 * 8);
+  const size_t o_binom = take(n64 * rn), o_desc = take(J.desc_bytes()), o_out = take((C + 1) * rn);
+  const size_t o_ab = take(fused ? 0 : C * rn), o_rn = take(fused ? 0 : C * rn), o_cdesc = take(fused ? 0 : C * 32);
+  const size_t o_ops = take(fused ? 0 : C * sizeof(Prod3Operand)), o_midx = take(fused ? 0 : C * 4);
+  uint8_t* dev = (uint8_t*)c->buf("resp_io", off);
+  if (!dev) {
+    c->fail("%s: device allocation failed (%zu bytes)", who, off);
+    return FSDKR_E_OOM;
+  }
+  auto DA = [&](size_t o) { return (uint64_t)(uintptr_t)(dev + o); };
+  auto PU = [&](size_t o) { return reinterpret_cast<uint32_t*>(dev + o); };
+  for (size_t k = 0; k < J.size(); ++k) {   // offsets -> device addresses
+    J.base_ptr[k] += (uint64_t)(uintptr_t)dev;
+    J.exp_ptr[k] += (uint64_t)(uintptr_t)dev;
+  }
+  std::vector<uint32_t> ha(n * nn), hb(n * 8, 0u), hbp(n64 * nl, 0u);
+  std::vector<uint64_t> hnp(n64, DA(o_N));
+  for (size_t k = 0; k < n; ++k) {
+    const uint32_t p = row[k];
+    memcpy(&ha[k * nn], a_enc + (size_t)p * nn, rn);
+    hnp[k] = DA(o_N + n_idx[p] * rl);
+    if (pad[k]) continue;   // b = 0, beta' = 0
+    memcpy(&hb[k * 8], b + (size_t)p * 8, 32);
+    memcpy(&hbp[k * nl], beta_prim + (size_t)p * nl, rl);
+  }
+  std::vector<uint8_t> desc, cdesc;
+  J.pack(desc);
+  std::vector<Prod3Operand> ops;
+  std::vector<uint32_t> midx;
+  if (!fused) {
+    ModexpJob Jc;   // a_enc^b: 256-bit secret exponents
+    Jc.k32 = nn;
+    for (uint32_t p = 0; p < count; ++p) Jc.add(DA(o_a + p * rn), nn, DA(o_b + (size_t)p * 32), 8, 256, n_idx[p]);
+    Jc.pack(cdesc);
+    ops.resize(C);
+    midx.assign(n_idx, n_idx + count);
+    for (uint32_t p = 0; p < count; ++p)
+      ops[p] = Prod3Operand{DA(o_ab + p * rn), DA(o_rn + p * rn), DA(o_binom + p * rn), nn, nn, nn, 0};
+  }
+  hipStream_t st = c->stream;
+  auto up = [&](size_t o, const void* src, size_t bytes) {
+    return bytes ? c->hip_check(hipMemcpyAsync(dev + o, src, bytes, hipMemcpyHostToDevice, st), "H2D respond") : (int)FSDKR_OK;
+  };
+  auto run = [&]() -> int {
+    int rc;
+    if ((rc = up(o_N, ns, nk * rl)) || (rc = up(o_NN, NN.data(), nk * rn)) || (rc = up(o_r, r, C * rl)) ||
+        (rc = up(o_a, ha.data(), n * rn)) || (rc = up(o_b, hb.data(), n * 32)) || (rc = up(o_bp, hbp.data(), n64 * rl)) ||
+        (rc = up(o_np, hnp.data(), n64 * 8)) || (rc = up(o_desc, desc.data(), desc.size())) ||
+        (rc = up(o_cdesc, cdesc.data(), cdesc.size())) || (rc = up(o_ops, ops.data(), ops.size() * sizeof(Prod3Operand))) ||
+        (rc = up(o_midx, midx.data(), midx.size() * 4)))
+      return rc;
+    uint32_t* cons = nullptr;
+    if ((rc = setup_moduli(c, nn, PU(o_NN), nk, &cons, "resp"))) return rc;
+    BinomCtArgs ba{PU(o_bp), (const uint64_t*)(dev + o_np), PU(o_binom), (uint32_t)n64};
+    c->mark("binom_ct", true);
+    rc = c->hip_check(launch_binom_ct(nl, ba, st), "binom_ct");
+    c->mark("binom_ct", false);
+    if (rc) return rc;
+    if (fused) {
+      SplitArgs head;
+      head.lo_bit = kMtaTailLo;
+      if ((rc = launch_modexp_desc(c, nn, (uint32_t)n, nbits, dev + o_desc, cons, PU(o_out), st, "mxt_resp", 0, G, flags,
+                                   &head)))
+        return rc;
+      const uint32_t w = choose_slide_window(nbits);   // the head's window (launch_modexp_desc)
+      const DevBuf tb = c->bufs["mxt_resp"], sb = c->bufs["mxt_resp_state"];
+      uint32_t* t2 = (uint32_t*)c->buf("mxt_resp_t2", n * 16 * 144 * 4);
+      if (!tb.ptr || !sb.ptr || !t2) {
+        c->fail("%s: device allocation failed (tail tables)", who);
+        return FSDKR_E_OOM;
+      }
+      const size_t n8 = n * 8, n4 = n * 4;
+      const uint8_t* d = dev + o_desc;
+      MtaTailArgs ta{(const uint64_t*)(d + n8), (const uint32_t*)(d + 2 * n8 + 2 * n4), (const uint32_t*)(d + 2 * n8 + 4 * n4),
+                     cons, (const uint32_t*)tb.ptr, (const uint32_t*)sb.ptr, w, PU(o_a), PU(o_b), PU(o_binom), t2,
+                     PU(o_out), (uint32_t)n};
+      c->mark("mta_tail_ct", true);
+      rc = c->hip_check(launch_mta_tail_ct(ta, st), "mta_tail_ct");
+      c->mark("mta_tail_ct", false);
+      if (rc) return rc;
+    } else {
+      {
+        CtScope ct(c);
+        if ((rc = launch_modexp_desc(c, nn, count, 256, dev + o_cdesc, cons, PU(o_ab), st, "mxt_resp_ct"))) return rc;
+      }
+      if ((rc = launch_modexp_desc(c, nn, (uint32_t)J.size(), 32 * nl, dev + o_desc, cons, PU(o_rn), st, "mxt_resp", 0, G,
+                                   flags)))
+        return rc;
+      Prod3Args pa{(const Prod3Operand*)(dev + o_ops), PU(o_midx), cons, PU(o_out), count};
+      c->mark("prod3", true);
+      rc = c->hip_check(launch_prod3(nn, pa, st), "prod3 respond");
+      c->mark("prod3", false);
+      if (rc) return rc;
+    }
+    return c->hip_check(hipMemcpyAsync(out, dev + o_out, C * rn, hipMemcpyDeviceToHost, st), "D2H respond");
+  };
+  const int rc = run();
+  // scrub what held b, beta', r or a value made from them: the operand image, the
+  // head's window table and state (powers of r), the regular-access table
+  int rs = FSDKR_OK;
+  for (const char* name : {"resp_io", "mxt_resp", "mxt_resp_state", "mxt_resp_t2", "mxt_resp_ct"}) {
+    const int q = scrub(c, name);
+    if (!rs) rs = q;
+  }
+  const int ry = c->sync();
+  wipe(hb);   // the host rows of b and beta', once the uploads are done with them
+  wipe(hbp);
+  return rc ? rc : rs ? rs : ry;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fsdkr_mta_respond(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, const uint32_t* a_enc, const uint32_t* b,
+                      const uint32_t* beta_prim, const uint32_t* r, const uint32_t* n_idx, const uint32_t* ns,
+                      uint32_t n_keys, uint32_t* out) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return FSDKR_E_ARG;
+  return mta_respond_impl(c, "fsdkr_mta_respond", nl, count, a_enc, b, beta_prim, r, n_idx, ns, n_keys, out, true);
+}
+
+int fsdkr_mta_respond_unfused(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, const uint32_t* a_enc, const uint32_t* b,
+                              const uint32_t* beta_prim, const uint32_t* r, const uint32_t* n_idx, const uint32_t* ns,
+                              uint32_t n_keys, uint32_t* out) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return FSDKR_E_ARG;
+  return mta_respond_impl(c, "fsdkr_mta_respond_unfused", nl, count, a_enc, b, beta_prim, r, n_idx, ns, n_keys, out, false);
 }
 
 }  // extern "C"

@@ -182,6 +182,37 @@ struct EcMsmCtArgs {        // out[o] = sum_j scalars[o][j] * points[o][j]
   uint32_t* scratch;        // [count_pad][terms][24] projective terms (EcMsmArgs' layout)
 };
 
+// Bob's MtA response (mta_ct.hip): the constant-time joint tail of the split chain
+// r^N a_enc^b (1 + beta' N) mod N^2 at 128 limbs, 8 lanes per chain.  Whole waves,
+// no bound check: every per-instance array has count_pad rows, in launch order.
+constexpr uint32_t kMtaTailPad = 8;    // instances per wave
+constexpr uint32_t kMtaTailLo = 256;   // the head's lo_bit: b < 2^256 rides the tail
+
+struct MtaTailArgs {
+  const uint64_t* exp_ptr;  // [count_pad] N's limbs (at least 8), shared by the instances of every wave
+  const uint32_t* mod_idx;  // [count_pad] row of consts
+  const uint32_t* out_idx;  // [count_pad] output row
+  const uint32_t* consts;   // mod_setup rows of the 144-digit class (N^2 and its scaled block)
+  const uint32_t* table;    // the head's odd-power table [count_pad][2^(window-1) + 1][144]
+  const uint32_t* state;    // the head's accumulator [count_pad][144]
+  uint32_t window;          // the head's sliding-window width
+  const uint32_t* a_enc;    // [count_pad][128] reduced mod N^2 (public)
+  const uint32_t* b;        // [count_pad][8] SECRET
+  const uint32_t* binom;    // [count_pad][128] 1 + beta' N (binom_ct_kernel) SECRET
+  uint32_t* table2;         // [count_pad][16][144] scratch: a_enc^u
+  uint32_t* out;            // rows of 128 limbs
+  uint32_t count_pad;       // a multiple of kMtaTailPad
+};
+
+struct BinomCtArgs {        // out = 1 + s * n for nl-limb factors, every limb of s multiplied in
+  const uint32_t* s;        // [count_pad][nl] SECRET
+  const uint64_t* n_ptr;    // [count_pad] nl limbs each
+  uint32_t* out;            // [count_pad][2 nl]
+  uint32_t count_pad;       // a multiple of 64
+};
+
+hipError_t launch_mta_tail_ct(const MtaTailArgs& a, hipStream_t st);
+hipError_t launch_binom_ct(uint32_t nl, const BinomCtArgs& a, hipStream_t st);   // nl = 64 or 96
 hipError_t launch_binom(const BinomArgs& a, hipStream_t st);
 hipError_t launch_ped_hash(const PedHashArgs& a, hipStream_t st);
 hipError_t launch_alice_hash(const AliceHashArgs& a, hipStream_t st);

@@ -150,6 +150,11 @@ def lib():
     L.fsdkr_bob_verify_unfused.argtypes = L.fsdkr_bob_verify.argtypes
     L.fsdkr_bob_verify_unfused.restype = ctypes.c_int
     L.fsdkr_modexp_batch_ct.restype = ctypes.c_int
+    L.fsdkr_mta_respond.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p,
+                                    ctypes.c_uint32, u32p]
+    L.fsdkr_mta_respond.restype = ctypes.c_int
+    L.fsdkr_mta_respond_unfused.argtypes = L.fsdkr_mta_respond.argtypes
+    L.fsdkr_mta_respond_unfused.restype = ctypes.c_int
     L.fsdkr_modexp_batch_device.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, ctypes.c_uint32,
                                             ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp]
     L.fsdkr_modexp_batch_device.restype = ctypes.c_int
@@ -588,6 +593,25 @@ class Context:
         self.check(self._lib.fsdkr_paillier_encrypt(self._h, nl, len(ms), _ptr(Mm), ml, _ptr(Rr), _ptr(I), _ptr(Nn),
                                                     len(ns), _ptr(O)))
         return limbs_to_ints(O)
+
+    def mta_respond(self, a_encs, bs, beta_prims, rs, ns, n_idx, nl, fused=True):
+        """Bob's MtA response [a_enc^b (1 + beta' N) r^N mod N^2] for N = ns[n_idx[k]]
+        (range_proofs.rs:688-704; fsdkr_mta_respond).  bs (< 2^256), beta_prims and
+        rs (< N) are SECRET and run in regular access; a_encs are reduced mod N^2.
+        fused=False: the separate chains of fsdkr_mta_respond_unfused (A/B timing)."""
+        count = len(a_encs)
+        if not (len(bs) == len(beta_prims) == len(rs) == len(n_idx) == count):
+            raise ValueError("mta_respond: argument lists differ in length")
+        A = ints_to_limbs(list(a_encs), 2 * nl) if count else np.zeros((1, 2 * nl), dtype=np.uint32)
+        B = ints_to_limbs(list(bs), 8) if count else np.zeros((1, 8), dtype=np.uint32)
+        Bp = ints_to_limbs(list(beta_prims), nl) if count else np.zeros((1, nl), dtype=np.uint32)
+        Rr = ints_to_limbs(list(rs), nl) if count else np.zeros((1, nl), dtype=np.uint32)
+        Nn = ints_to_limbs(list(ns), nl)
+        I = np.ascontiguousarray(np.asarray(list(n_idx) or [0], dtype=np.uint32))
+        O = np.zeros((max(1, count), 2 * nl), dtype=np.uint32)
+        fn = self._lib.fsdkr_mta_respond if fused else self._lib.fsdkr_mta_respond_unfused
+        self.check(fn(self._h, nl, count, _ptr(A), _ptr(B), _ptr(Bp), _ptr(Rr), _ptr(I), _ptr(Nn), len(ns), _ptr(O)))
+        return limbs_to_ints(O[:count])
 
     def pdl_u1_check(self, s1s, es, Qs, u1s):
         """[G*(s1 mod q) + Q*(q - e mod q) == u1] per pair (uint8 0/1)."""

@@ -9,7 +9,12 @@ verify_bob   `count` independent proofs in one device pass (fsdkr_bob_verify):
              class, keys of up to 3072 bits in the 96-limb class (one per call).
 generate_bob the prover (BobZkpRound1 / Round2, BobProof::generate), batched
              per round over the existing entry points; secret exponents run
-             through the regular-access kernel."""
+             through the regular-access kernel.
+respond      Bob's side of one exchange ("Bob follows MtA", :688-704): the
+             response mta_out = a_enc^b * Enc(beta'; r) on the device
+             (fsdkr_mta_respond: one constant-time chain per response for keys of
+             up to 2048 bits), then its proofs (generate_bob).
+finish       Alice's last step: alpha = Dec(mta_out) mod q."""
 import math
 
 import numpy as np
@@ -251,3 +256,72 @@ def generate_bob(items, rng, ctx=None, check=False):
                       e * sigma + tau)
         out.append(BobProofExt(pf, pts[n + k]) if check else pf)
     return out
+
+
+def respond(a_encs, bs, eks, statements, rng, ctx=None, check=False):
+    """Bob follows MtA (range_proofs.rs:688-715) for every exchange k: Alice's
+    ciphertext a_encs[k] under her key eks[k], Bob's secret scalar bs[k] (0 <= b <
+    2^256) and Alice's (N~, h1, h2) statements[k].
+
+    Per exchange the draws go through `rng` in the reference test's order (:696-697):
+    beta' = sample_below(N), then r = sample_below(N); then ONE device call computes
+    every mta_out = a_enc^b (1 + beta' N) r^N mod N^2 (Context.mta_respond, at the
+    width class of the call's keys, width_class; a_enc is reduced mod N^2), and
+    ONE generate_bob call over the same rng proves them.
+
+    Returns (mta_outs, betas, proofs): the responses, Bob's additive shares
+    beta = -beta' mod q, and BobProofs (check=True: BobProofExts, whose verifier
+    takes X = G*b)."""
+    ctx = _ctx(ctx)
+    a_encs, bs, eks, statements = list(a_encs), list(bs), list(eks), list(statements)
+    n = len(a_encs)
+    if not (len(bs) == len(eks) == len(statements) == n):
+        raise ValueError("respond: argument lists differ in length")
+    for b in bs:
+        if b < 0 or b >> 256:
+            raise ValueError("respond: b must satisfy 0 <= b < 2^256")
+    if n == 0:
+        return [], [], []
+    nl = width_class(eks, statements)
+    draws = []
+    for ek in eks:
+        beta_prim = rng.sample_below(ek.n)
+        draws.append((beta_prim, rng.sample_below(ek.n)))
+    ns, n_row = [], {}
+    for ek in eks:
+        if ek.n not in n_row:
+            n_row[ek.n] = len(ns)
+            ns.append(ek.n)
+    a_red = [a % ek.nn for a, ek in zip(a_encs, eks)]
+    mta_outs = ctx.mta_respond(a_red, bs, [d[0] for d in draws], [d[1] for d in draws], ns,
+                               [n_row[ek.n] for ek in eks], nl)
+    items = [(a, m, b, d[0], ek, st, d[1]) for a, m, b, d, ek, st in zip(a_encs, mta_outs, bs, draws, eks, statements)]
+    proofs = generate_bob(items, rng, ctx=ctx, check=check)
+    return mta_outs, [(-d[0]) % Q for d in draws], proofs
+
+
+def finish(mta_outs, dks, ctx=None):
+    """Alice's last step of MtA: alpha_k = Dec(mta_outs[k]) mod q under her
+    DecryptionKey dks[k] (Context.paillier_decrypt for one key, paillier_decrypt_many
+    otherwise), so that alpha + beta = a b mod q with respond's beta."""
+    ctx = _ctx(ctx)
+    mta_outs, dks = list(mta_outs), list(dks)
+    if len(mta_outs) != len(dks):
+        raise ValueError("finish: argument lists differ in length")
+    if not mta_outs:
+        return []
+    keys, row = [], {}
+    for dk in dks:
+        if (dk.p, dk.q) not in row:
+            row[(dk.p, dk.q)] = len(keys)
+            keys.append((dk.p, dk.q))
+    bits = max(max(p.bit_length(), q.bit_length()) for p, q in keys) * 2
+    nl = next((c for c in NL_CLASSES if bits <= 32 * c), None)
+    if nl is None:
+        raise UnsupportedInput(f"finish: key wider than {32 * NL_CLASSES[-1]} bits")
+    if len(keys) == 1:
+        ms = ctx.paillier_decrypt(mta_outs, keys[0][0], keys[0][1], nl)
+    else:
+        ms = ctx.paillier_decrypt_many(mta_outs, [row[(dk.p, dk.q)] for dk in dks], [k[0] for k in keys],
+                                       [k[1] for k in keys], nl)
+    return [m % Q for m in ms]

@@ -7,6 +7,8 @@ Field order and names follow the struct declarations:
   JoinMessage        add_party_message.rs:34-45
   PDLwSlackProof     zk_pdl_with_slack.rs:39-50 (_phantom: PhantomData -> null)
   AliceProof         range_proofs.rs:100-108   (_phantom -> null)
+  BobProof           range_proofs.rs:346-356   (t, z, e, s, s1, s2, t1, t2, _phantom -> null)
+  BobProofExt        range_proofs.rs:520-523   ({proof, u})
   RingPedersenStatement / Proof  ring_pedersen_proof.rs:28-38, 77-84 (phantom skipped)
 Dependency encodings, restated from the published crates and NOT checked
 against their code (parity unpinned: curv-kzen 0.10, kzen-paillier 0.4.3,
@@ -139,6 +141,23 @@ def _unalice(d):
     return T.AliceProof(_unbi(d["z"]), _unbi(d["e"]), _unbi(d["s"]), _unbi(d["s1"]), _unbi(d["s2"]))
 
 
+def bob_proof_to_obj(p):
+    return {"t": _bi(p.t), "z": _bi(p.z), "e": _bi(p.e), "s": _bi(p.s), "s1": _bi(p.s1), "s2": _bi(p.s2),
+            "t1": _bi(p.t1), "t2": _bi(p.t2), "_phantom": None}
+
+
+def bob_proof_from_obj(d):
+    return T.BobProof(*(_unbi(d[f]) for f in ("t", "z", "e", "s", "s1", "s2", "t1", "t2")))
+
+
+def bob_proof_ext_to_obj(p):
+    return {"proof": bob_proof_to_obj(p.proof), "u": _pt(p.u)}
+
+
+def bob_proof_ext_from_obj(d):
+    return T.BobProofExt(bob_proof_from_obj(d["proof"]), _unpt(d["u"]))
+
+
 def _ck(p):
     return {"sigma_vec": [_bi(s) for s in p.sigma_vec]}
 
@@ -220,11 +239,14 @@ def local_key_from_obj(d):
 
 _KINDS = {"RefreshMessage": (refresh_message_to_obj, refresh_message_from_obj),
           "JoinMessage": (join_message_to_obj, join_message_from_obj),
-          "LocalKey": (local_key_to_obj, local_key_from_obj)}
+          "LocalKey": (local_key_to_obj, local_key_from_obj),
+          "BobProof": (bob_proof_to_obj, bob_proof_from_obj),
+          "BobProofExt": (bob_proof_ext_to_obj, bob_proof_ext_from_obj)}
 
 
 def dumps(obj):
-    """serde_json text of a RefreshMessage / JoinMessage / LocalKey (compact, field order kept)."""
+    """serde_json text of a RefreshMessage / JoinMessage / LocalKey / BobProof / BobProofExt
+    (compact, field order kept)."""
     kind = type(obj).__name__
     if kind not in _KINDS:
         raise TypeError(f"no wire format for {kind}")
@@ -232,9 +254,11 @@ def dumps(obj):
 
 
 def loads(text, kind):
-    """Decode serde_json text of `kind` ("RefreshMessage", "JoinMessage", "LocalKey")."""
+    """Decode serde_json text of `kind` ("RefreshMessage", "JoinMessage", "LocalKey", "BobProof",
+    "BobProofExt")."""
     return _KINDS[kind][1](json.loads(text))
 
 
 __all__ = ["dumps", "loads", "refresh_message_to_obj", "refresh_message_from_obj", "join_message_to_obj",
-           "join_message_from_obj", "local_key_to_obj", "local_key_from_obj"]
+           "join_message_from_obj", "local_key_to_obj", "local_key_from_obj", "bob_proof_to_obj",
+           "bob_proof_from_obj", "bob_proof_ext_to_obj", "bob_proof_ext_from_obj"]

@@ -381,6 +381,44 @@ int fsdkr_bob_verify(fsdkr_ctx* ctx, const fsdkr_bob_batch* batch, uint8_t* verd
  * fsdkr_bob_verify (tools/bench_mta.py), not a second implementation to call. */
 int fsdkr_bob_verify_unfused(fsdkr_ctx* ctx, const fsdkr_bob_batch* batch, uint8_t* verdict);
 
+/* ---- Bob's MtA response ------------------------------------------------------
+ * The value Bob's range proofs are about (range_proofs.rs:688-704, "Bob follows
+ * MtA"): out = Paillier::add(Paillier::mul(ek, a_enc, b), Enc(beta_prim; r))
+ *            = a_enc^b (1 + beta_prim N) r^N mod N^2
+ * (kzen-paillier Mul, Add and encrypt_with_chosen_randomness), `count` responses
+ * in one device pass, N = ns[n_idx[i]] odd and above 1.  b, beta_prim and r are
+ * SECRET: no address, branch or trip count on the device depends on them, and
+ * before the call returns every device buffer that held one of them, or a value
+ * made from r alone (the window table and state of the r^N chain), is zeroed.
+ * a_enc is public and must be reduced modulo N^2 (FSDKR_E_ARG otherwise); b is any
+ * value below 2^256; beta_prim and r are below N (not checked: they are secret).
+ * nl = 64 (keys of up to 2048 bits): ONE chain of bits(N) squarings per response,
+ * the sliding-window head of r^N over N's bits >= 256, then a constant-time joint
+ * tail that carries a_enc^b along the last 256 squarings (64 fixed 4-bit digits of
+ * b, every table row read by a masked scan of all 16) and multiplies 1 + beta_prim N
+ * in as it leaves Montgomery form.  The host orders and pads the instances so that
+ * every wave holds one key.  The tail runs at 8 lanes (the head at 16, 8 or 4 by
+ * batch size, at 8 when forced): a context forced to another lane count
+ * (fsdkr_ctx_set_modexp_group) gets FSDKR_E_ARG.
+ * nl = 96 (up to 3072 bits): the same values from separate chains (a_enc^b through
+ * the regular-access kernel of fsdkr_modexp_batch_ct, r^N as fsdkr_paillier_encrypt
+ * runs it) and one modular product on the device.
+ * Any other nl: FSDKR_E_UNSUPPORTED.  Even N or N <= 1: FSDKR_E_ARG.  count == 0: OK. */
+int fsdkr_mta_respond(fsdkr_ctx* ctx, uint32_t nl, uint32_t count,
+                      const uint32_t* a_enc,      /* [count][2nl], reduced mod N^2 by the caller */
+                      const uint32_t* b,          /* [count][8], any value < 2^256: SECRET */
+                      const uint32_t* beta_prim,  /* [count][nl], < N: SECRET */
+                      const uint32_t* r,          /* [count][nl], < N: SECRET */
+                      const uint32_t* n_idx, const uint32_t* ns, uint32_t n_keys,
+                      uint32_t* out);             /* [count][2nl] */
+
+/* The same values with the separate chains and the product at nl = 64 as well: the
+ * A/B counterpart of fsdkr_mta_respond (tools/bench_mta_respond.py), not a second
+ * implementation to call.  It accepts any forced lane count. */
+int fsdkr_mta_respond_unfused(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, const uint32_t* a_enc, const uint32_t* b,
+                              const uint32_t* beta_prim, const uint32_t* r, const uint32_t* n_idx,
+                              const uint32_t* ns, uint32_t n_keys, uint32_t* out);
+
 /* Which prestarted parts the last fsdkr_collect_prepare[_multi] reused (bit
  * mask): 1 GA chains, 2 fixed-base tables, 4 correct-key job, 8 ring-Pedersen
  * T^Z exponents (multi-session).  0 before any prepare.  Diagnostic (tests
