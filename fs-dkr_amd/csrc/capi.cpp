@@ -382,6 +382,7 @@ int launch_modexp_desc(Ctx* c, uint32_t k32, uint32_t count, uint32_t exp_bits, 
       return FSDKR_E_ARG;
     }
     a.nadic = split->nadic;
+    a.nadic_tail_full = (c->flags & FSDKR_CFG_GA_TAIL_FULLWIDTH) ? 1u : 0u;
     a.lo_bit = split->lo_bit;
     a.tail = split->tail ? 1u : 0u;
     a.state = (uint32_t*)c->buf((base + "_state").c_str(), (size_t)count * KD * 4);

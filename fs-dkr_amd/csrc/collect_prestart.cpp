@@ -13,6 +13,8 @@ namespace fsdkr {
 //   (r, (N' - q) mod N')                  M(R): (q, r) = divmod(R^2 mod N'^2, N'), so that
 //                                         r - ((N' - q) mod N') N' = R^2 (mod N'^2)
 //   C1 = R^3 mod N^2, C2 = -N' C1 mod N^2 the tail's hand-over: x0 C1 + x1 C2 = X R^3
+//   (r2, (N' - q2) mod N')                P2: 2^2048 R^2 mod N'^2 split like M(R); the tail
+//                                         enters base2 = lo + 2^2048 hi as lo M(R) + hi P2
 // with R = 2^(29*72).
 void nadic_consts(const uint32_t* N, uint32_t nl, uint32_t* out) {
   constexpr uint32_t kM29 = (1u << 29) - 1;
@@ -41,6 +43,10 @@ void nadic_consts(const uint32_t* N, uint32_t nl, uint32_t* out) {
   digits(nq, out + kNadicR1, 72);
   digits(C1, out + kNadicC1, 144);
   digits(C2, out + kNadicC2, 144);
+  hbn::Limbs q2, r2;
+  hbn::divmod_knuth(hbn::mod(hbn::shl(one, 2048 + 2 * 29 * 72), hbn::mul(Np, Np)), Np, &q2, &r2);
+  digits(r2, out + kNadicP2, 72);
+  digits(q2.empty() ? hbn::Limbs{} : hbn::sub(Np, q2), out + kNadicP2 + 72, 72);
 }
 
 

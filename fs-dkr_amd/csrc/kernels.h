@@ -54,9 +54,9 @@ struct ModexpArgs {
   uint32_t* table2 = nullptr;       // [count][16][KD]
   // N-adic head (modexp_nadic_head_kernel; 4096-bit class N^2 of a 2048-bit N, 16
   // lanes, window 7): rows of kNadicStride words per modulus (nadic_consts, host).
-  // The head then leaves the raw pair (x0 | x1) in state, and the tail launched with
-  // the same pointer converts it and runs the low bits of exp over its own
-  // 16-entry table of base powers (built in `table`) instead of the head's table.
+  // The head then leaves the raw pair (x0 | x1) in state and its 64 odd powers in
+  // `table`; the tail launched with the same pointer (modexp_nadic_tail_kernel) goes
+  // on in pair form over that table, with its joint table in pair form too.
   const uint32_t* nadic = nullptr;
   // A second extra base of the tail (modexp_tail_kernel J3; needs base2_ptr, not the
   // N-adic head): out = base^exp * base2^exp2 * base3^exp3, base3 read as base2 is,
@@ -69,12 +69,18 @@ struct ModexpArgs {
   const uint32_t* exp3_len = nullptr;    // [count] limbs
   uint32_t* table3 = nullptr;            // [count][16][KD]
   uint32_t exp3_bits = 0;
+  // 1: the N-adic head's tail converts the pair at its entry and runs full width over
+  // its own 16-entry table of base powers (modexp_tail_kernel NA), for A/B runs
+  uint32_t nadic_tail_full = 0;
 };
 
 // Per-modulus constants of the N-adic head, 72 digits of 29 bits each unless noted:
 // N' = N k0 (k0 = -N^-1 mod 2^29) | r | (N' - q) mod N' with (q, r) = divmod(R^2 mod
-// N'^2, N'), R = 2^(29*72) | C1 = R^3 mod N^2 (144 digits) | C2 = -N' C1 mod N^2 (144)
-constexpr int kNadicNp = 0, kNadicR0 = 72, kNadicR1 = 144, kNadicC1 = 216, kNadicC2 = 360, kNadicStride = 512;
+// N'^2, N'), R = 2^(29*72) | C1 = R^3 mod N^2 (144 digits) | C2 = -N' C1 mod N^2 (144) |
+// r2 | (N' - q2) mod N' with (q2, r2) = divmod(2^2048 R^2 mod N'^2, N') (the N-adic
+// tail's entry of the high half of base2)
+constexpr int kNadicNp = 0, kNadicR0 = 72, kNadicR1 = 144, kNadicC1 = 216, kNadicC2 = 360, kNadicP2 = 504,
+              kNadicStride = 656;
 constexpr uint32_t kNadicWindow = 7;
 
 int shape_digits(uint32_t k32);   // KD for a K32-limb modulus class (0 if unsupported)

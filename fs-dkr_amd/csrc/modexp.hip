@@ -511,7 +511,8 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_slide_kernel(const ModexpArgs
 // (R >= 2^11 N').
 // The schedule is modexp_slide_kernel's head: wave-uniform sliding windows of
 // kNadicWindow bits over the exponent bits >= lo_bit.  The raw pair goes to
-// state; the tail (modexp_tail_kernel NA) brings it into its full-width form.
+// state and the 64 odd powers stay in the table, whatever the exponent: the tail
+// (modexp_nadic_tail_kernel) carries on in pair form over both.
 __global__ __launch_bounds__(BLOCK) void modexp_nadic_head_kernel(const ModexpArgs a) {
   using MT = Mont29<72, 8>;
   constexpr int L = MT::L, KD = 144, G = 16;
@@ -567,18 +568,21 @@ __global__ __launch_bounds__(BLOCK) void modexp_nadic_head_kernel(const ModexpAr
 #pragma unroll
     for (int j = 0; j < L; ++j) row[g * L + j] = acc[j];
   };
-  const bool none = top < lo;   // no bits for the head: the pair of 1 (Montgomery form)
-  {   // x = (base, 0) M(R)
+  // no bits for the head: the pair of 1 (Montgomery form) goes to state, and the
+  // table is built all the same (the N-adic tail's windows of the low bits read it)
+  const bool none = top < lo;
+  for (int pass = none ? 0 : 1; pass < 2; ++pass) {   // (1, 0) M(R) for state, then x = (base, 0) M(R)
     uint32_t b[L];
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int j = 0; j < L; ++j) {
       const int d = g * L + j;
       b[j] = C[kNadicR0 + d];   // r in group A, (N' - q) in group B
-      if (!hi) stream[d] = none ? (d == 0 ? 1u : 0u) : digit_of(B, blen, d);
+      if (!hi) stream[d] = pass == 0 ? (d == 0 ? 1u : 0u) : digit_of(B, blen, d);
     }
     __builtin_amdgcn_wave_barrier();
     M.product_pair(acc, b, stream);
+    if (pass == 0) store(a.state + (size_t)inst * KD);
   }
   // the squarings: A: b = x0, B: b = 2 x1
   auto square = [&]() {
@@ -590,65 +594,64 @@ __global__ __launch_bounds__(BLOCK) void modexp_nadic_head_kernel(const ModexpAr
     for (int j = 0; j < L; ++j) b[j] = acc[j] << sh_hi;
     M.product_pair(acc, b, stream);
   };
-  if (!none) {
-    store(T);
-    square();
-    store(T + (size_t)tw * KD);   // x^2
-    load(T);
-    // phase 2: T[jt] = T[jt-1] x^2;  3: the windows
-    int phase = tw > 1 ? 2 : 3, i = top, pend_mul = -1;
-    uint32_t jt = 1, pend_sq = 0;
-    for (;;) {
-      if (phase == 3) {
-        if (i == top) {   // the first window: its odd power, no squarings of 1
-          int jl;
-          const uint32_t d = window(i, &jl);
-          load(T + (size_t)(d >> 1) * KD);
-          i = jl - 1;
-        }
-        if (pend_sq == 0 && pend_mul < 0)
-          while (i >= lo && !bit(i)) {
-            ++pend_sq;
-            --i;
-          }
-        for (; pend_sq; --pend_sq) square();   // the squarings between two products, in a loop of their own
-      }
-      const uint32_t* src;
-      if (phase == 2) {
-        src = T + (size_t)tw * KD;
-      } else if (pend_mul >= 0) {
-        src = T + (size_t)pend_mul * KD;
-        pend_mul = -1;
-      } else if (i < lo) {
-        break;
-      } else {   // bit i is set: its window's squarings, then its product
+  store(T);
+  square();
+  store(T + (size_t)tw * KD);   // x^2
+  load(T);
+  // phase 2: T[jt] = T[jt-1] x^2;  3: the windows
+  int phase = tw > 1 ? 2 : 3, i = top, pend_mul = -1;
+  uint32_t jt = 1, pend_sq = 0;
+  for (;;) {
+    if (phase == 3) {
+      if (none) return;   // the table is built, state is written
+      if (i == top) {   // the first window: its odd power, no squarings of 1
         int jl;
         const uint32_t d = window(i, &jl);
-        pend_sq = (uint32_t)(i - jl + 1);
-        pend_mul = (int)(d >> 1);
+        load(T + (size_t)(d >> 1) * KD);
         i = jl - 1;
-        continue;
       }
-      // the table product, one coupled pass: A: y0 x0, B: y0 x1 + x0 y1 + M
-      uint32_t y[L];
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int j = 0; j < L; ++j) y[j] = src[g * L + j];
-      if (!hi) {   // the two streamed operands: y0 and the old x0
-#pragma unroll
-        for (int j = 0; j < L; ++j) {
-          stream[g * L + j] = y[j];
-          stream[72 + g * L + j] = acc[j];
+      if (pend_sq == 0 && pend_mul < 0)
+        while (i >= lo && !bit(i)) {
+          ++pend_sq;
+          --i;
         }
-      }
+      for (; pend_sq; --pend_sq) square();   // the squarings between two products, in a loop of their own
+    }
+    const uint32_t* src;
+    if (phase == 2) {
+      src = T + (size_t)tw * KD;
+    } else if (pend_mul >= 0) {
+      src = T + (size_t)pend_mul * KD;
+      pend_mul = -1;
+    } else if (i < lo) {
+      break;
+    } else {   // bit i is set: its window's squarings, then its product
+      int jl;
+      const uint32_t d = window(i, &jl);
+      pend_sq = (uint32_t)(i - jl + 1);
+      pend_mul = (int)(d >> 1);
+      i = jl - 1;
+      continue;
+    }
+    // the table product, one coupled pass: A: y0 x0, B: y0 x1 + x0 y1 + M
+    uint32_t y[L];
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-      for (int j = 0; j < L; ++j) y[j] &= m_hi;   // A: 0, B: y1
-      __builtin_amdgcn_wave_barrier();
-      M.product_pair2(acc, acc, y, stream, stream + 72);
-      if (phase == 2) {
-        store(T + (size_t)jt * KD);
-        if (++jt == tw) phase = 3;
+    for (int j = 0; j < L; ++j) y[j] = src[g * L + j];
+    if (!hi) {   // the two streamed operands: y0 and the old x0
+#pragma unroll
+      for (int j = 0; j < L; ++j) {
+        stream[g * L + j] = y[j];
+        stream[72 + g * L + j] = acc[j];
       }
+    }
+#pragma unroll
+    for (int j = 0; j < L; ++j) y[j] &= m_hi;   // A: 0, B: y1
+    __builtin_amdgcn_wave_barrier();
+    M.product_pair2(acc, acc, y, stream, stream + 72);
+    if (phase == 2) {
+      store(T + (size_t)jt * KD);
+      if (++jt == tw) phase = 3;
     }
   }
 #pragma unroll
@@ -907,6 +910,202 @@ __global__ __launch_bounds__(BLOCK, 2) void modexp_tail_kernel(const ModexpArgs 
   for (int k = 0; k < LO; ++k) O[g * LO + k] = limb_of(stream, KD, g * LO + k);
 }
 
+// The joint tail of the N-adic head, in the head's pair form (ModexpArgs.nadic; the
+// full-width modexp_tail_kernel NA does the same work under nadic_tail_full).  It
+// resumes the raw pair from state and runs the exponent bits below lo with the
+// head's squaring, the head's sliding windows carried on over the low bits (its 64
+// odd powers are still in `table`, read only here) and, every 4th bit, the pair
+// T2[digit of exp2].  T2[u] = pair of base2^u R (table2, 144-word rows, x0 first):
+//   T2[0] = (1, 0) M(R)
+//   T2[1]: base2 = lo + 2^2048 hi < 2^4096 enters in one pass with both halves
+//          streamed (product_pair2): A: red(lo r + hi r2), B: red(lo nq + hi nq2 + M),
+//          M(R) = (r, nq), P2 = (r2, nq2) the pair of 2^2048 R^2 (kNadicP2).  lo <
+//          2^2048 <= R 2^-40 keeps the result within the chain's bound on x0, x1
+//          (tests/test_nadic_tail_model.py; split at the digit boundary 2^2088 it
+//          reached 1.41 N')
+//   T2[u] = T2[u-1] T2[1], the head's table product with T2[1].x0 left in the stream
+// The exit is the full-width tail's hand-over after the loop: Y = mont(x0, C1) +
+// mont(x1, C2) modulo (N^2)', then the product by 1 modulo N^2 itself.  Exact results,
+// bit-identical to modexp_tail_kernel's.
+__global__ __launch_bounds__(BLOCK) void modexp_nadic_tail_kernel(const ModexpArgs a) {
+  using MT = Mont29<72, 8>;
+  constexpr int L = MT::L, KD = 144, G = 16, K32 = 128;
+  constexpr int IPB = BLOCK / G;
+  __shared__ uint32_t lds[IPB * KD];
+  const int g = threadIdx.x % G;
+  const int li = threadIdx.x / G;
+  const uint32_t inst = blockIdx.x * (blockDim.x / G) + li;
+  if (inst >= a.count) return;
+  if (a.prio == 1) __builtin_amdgcn_s_setprio(1);
+  else if (a.prio == 2) __builtin_amdgcn_s_setprio(2);
+  else if (a.prio >= 3) __builtin_amdgcn_s_setprio(3);
+  uint32_t* stream = lds + li * KD;
+  const uint32_t* CN = a.nadic + (size_t)a.mod_idx[inst] * kNadicStride;
+  const bool hi = g >= 8;
+  uint32_t sh_hi = hi ? 1u : 0u, m_hi = hi ? 0xFFFFFFFFu : 0u;
+  asm volatile("" : "+v"(sh_hi), "+v"(m_hi));
+  MT M;
+  M.init_pair(g);
+#pragma unroll
+  for (int j = 0; j < L; ++j) M.n[j] = CN[kNadicNp + (g & 7) * L + j];
+  M.ninv = 1u;
+  const uint32_t tw = 1u << (kNadicWindow - 1);
+  const uint32_t* T = a.table + (size_t)inst * (tw + 1) * KD;   // the head's odd powers
+  const uint64_t ea = a.exp_ptr[inst];
+  const uint32_t* E = reinterpret_cast<const uint32_t*>(
+      ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ea >> 32)) << 32) |
+      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ea));
+  const int exp_limbs = __builtin_amdgcn_readfirstlane((int)a.exp_len[inst]);
+  auto bit = [&](int i) -> uint32_t { return (i >> 5) < exp_limbs ? (E[i >> 5] >> (i & 31)) & 1u : 0u; };
+  const int lo = (int)a.lo_bit;
+  uint32_t acc[L];
+  // the squaring and the table product of the head
+  auto square = [&]() {
+    __builtin_amdgcn_wave_barrier();
+    lds_put<KD, G>(stream, acc, g);
+    __builtin_amdgcn_wave_barrier();
+    uint32_t b[L];
+#pragma unroll
+    for (int j = 0; j < L; ++j) b[j] = acc[j] << sh_hi;
+    M.product_pair(acc, b, stream);
+  };
+  auto times = [&](const uint32_t* src) {   // A: y0 x0, B: y0 x1 + x0 y1 + M
+    uint32_t y[L];
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < L; ++j) y[j] = src[g * L + j];
+    if (!hi) {
+#pragma unroll
+      for (int j = 0; j < L; ++j) {
+        stream[g * L + j] = y[j];
+        stream[72 + g * L + j] = acc[j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < L; ++j) y[j] &= m_hi;
+    __builtin_amdgcn_wave_barrier();
+    M.product_pair2(acc, acc, y, stream, stream + 72);
+  };
+  const bool joint = a.base2_ptr != nullptr;
+  uint32_t* T2 = joint ? a.table2 + (size_t)inst * 16 * KD : nullptr;
+  const uint32_t* E2 = nullptr;
+  uint32_t e2len = 0;
+  if (joint) {
+    E2 = reinterpret_cast<const uint32_t*>(a.exp2_ptr[inst]);
+    e2len = a.exp2_len[inst];
+    const uint32_t* B2 = reinterpret_cast<const uint32_t*>(a.base2_ptr[inst]);
+    uint32_t b[L], b2[L];
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+      const int d = g * L + j;
+      b[j] = CN[kNadicR0 + d];    // r | nq
+      b2[j] = CN[kNadicP2 + d];   // r2 | nq2
+      if (!hi) stream[d] = d == 0 ? 1u : 0u;
+    }
+    __builtin_amdgcn_wave_barrier();
+    M.product_pair(acc, b, stream);
+#pragma unroll
+    for (int j = 0; j < L; ++j) T2[g * L + j] = acc[j];
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < L; ++j)   // lo's 72 digits, then hi's: each half is 64 limbs
+      stream[g * L + j] = digit_of(B2 + (hi ? 64 : 0), 64, (g & 7) * L + j);
+    __builtin_amdgcn_wave_barrier();
+    M.product_pair2(acc, b, b2, stream, stream + 72);
+#pragma unroll
+    for (int j = 0; j < L; ++j) T2[KD + g * L + j] = acc[j];
+    // the powers: T2[1].x0 stays in the stream's first half, its x1 in b
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+      if (!hi) stream[g * L + j] = acc[j];
+      b[j] = acc[j] & m_hi;
+    }
+    for (int u = 2; u < 16; ++u) {
+      __builtin_amdgcn_wave_barrier();
+      if (!hi) {
+#pragma unroll
+        for (int j = 0; j < L; ++j) stream[72 + g * L + j] = acc[j];
+      }
+      __builtin_amdgcn_wave_barrier();
+      M.product_pair2(acc, acc, b, stream, stream + 72);
+#pragma unroll
+      for (int j = 0; j < L; ++j) T2[(size_t)u * KD + g * L + j] = acc[j];
+    }
+  }
+  // bits lo-1 .. 0: square; the sliding window of E that ends at i multiplies
+  // T[d >> 1] in; every 4th bit the instance's exp2 digit multiplies T2[digit] in
+#pragma unroll
+  for (int j = 0; j < L; ++j) acc[j] = a.state[(size_t)inst * KD + g * L + j];
+  int pend_at = -1;
+  uint32_t pend_d = 0, ew = 0;
+  for (int i = lo - 1; i >= 0; --i) {
+    if ((i & 31) == 31 && joint) ew = ((uint32_t)(i >> 5) < e2len) ? E2[i >> 5] : 0u;
+    if (pend_at < 0 && bit(i)) {   // a window starts: its lowest set bit jl >= max(i - w + 1, 0)
+      int j = max(i - (int)kNadicWindow + 1, 0);
+      while (!bit(j)) ++j;
+      uint32_t d = 0;
+      for (int k = i; k >= j; --k) d = (d << 1) | bit(k);
+      pend_at = j;
+      pend_d = d;
+    }
+    square();
+    if (i == pend_at) {
+      times(T + (size_t)(pend_d >> 1) * KD);
+      pend_at = -1;
+    }
+    if (joint && (i & 3) == 0) times(T2 + (size_t)((ew >> (i & 31)) & 15u) * KD);
+  }
+  // exit: the pair into the full-width chain's form, Y = x0 C1 / R + x1 C2 / R = x R
+  // (mod N^2, R the 144-digit one), Y < 2 (N^2)'; then Y * 1 / R modulo N^2 itself
+  using MF = Mont29<KD, G>;
+  static_assert(MF::L == L, "pair and full-width rows hold 9 digits per lane");
+  const uint32_t* C0 = a.consts + (size_t)a.mod_idx[inst] * cons_stride(KD);
+  const uint32_t* C = C0 + cons_scaled(KD);
+  MF F;
+  F.init_lane(g);
+#pragma unroll
+  for (int j = 0; j < L; ++j) F.n[j] = C[g * L + j];
+  F.ninv = C[3 * KD];
+  uint32_t y[L];
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int j = 0; j < L; ++j) {
+    stream[g * L + j] = g < 8 ? acc[j] : 0u;   // x0, zero-extended
+    y[j] = CN[kNadicC1 + g * L + j];
+  }
+  __builtin_amdgcn_wave_barrier();
+  F.mul_s(y, y, stream);
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int j = 0; j < L; ++j) stream[(g ^ 8) * L + j] = g >= 8 ? acc[j] : 0u;   // x1 moves down to the low digits
+#pragma unroll
+  for (int j = 0; j < L; ++j) acc[j] = CN[kNadicC2 + g * L + j];
+  __builtin_amdgcn_wave_barrier();
+  F.mul_s(acc, acc, stream);
+#pragma unroll
+  for (int j = 0; j < L; ++j) acc[j] += y[j];
+  F.carry_exact(acc);
+#pragma unroll
+  for (int j = 0; j < L; ++j) F.n[j] = C0[g * L + j];
+  F.ninv = C0[3 * KD];
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int j = 0; j < L; ++j) stream[g * L + j] = (g == 0 && j == 0) ? 1u : 0u;
+  __builtin_amdgcn_wave_barrier();
+  F.mul(acc, acc, stream);
+  F.carry_exact(acc);
+  F.sub_if_ge(acc);
+  __builtin_amdgcn_wave_barrier();
+  lds_put<KD, G>(stream, acc, g);
+  __builtin_amdgcn_wave_barrier();
+  uint32_t* O = a.out + (size_t)(a.out_idx ? a.out_idx[inst] : inst) * K32;
+  constexpr int LO = K32 / G;
+#pragma unroll
+  for (int k = 0; k < LO; ++k) O[g * LO + k] = limb_of(stream, KD, g * LO + k);
+}
+
 // One instance per wave64 (the latency shape of small launches, e.g. a
 // multi-GPU rank's GA chains): lane g holds digits gL..gL+L-1 of every operand,
 // KR digits in the first KR/L lanes and zeros above; the streamed operand of each
@@ -1048,6 +1247,15 @@ static hipError_t launch_modexp_nadic_head(const ModexpArgs& a, hipStream_t st) 
   return hipGetLastError();
 }
 
+static hipError_t launch_modexp_nadic_tail(const ModexpArgs& a, hipStream_t st) {
+  const uint32_t bs = block_threads(a.count * 16);
+  const uint32_t ipb = bs / 16;
+  const uint32_t blocks = (a.count + ipb - 1) / ipb;
+  if (blocks == 0) return hipSuccess;
+  hipLaunchKernelGGL(modexp_nadic_tail_kernel, dim3(blocks), dim3(bs), 0, st, a);
+  return hipGetLastError();
+}
+
 template <int KD, int G, int K32, bool QS, bool NA = false, bool J3 = false>
 static hipError_t launch_modexp_tail(const ModexpArgs& a, hipStream_t st) {
   const uint32_t bs = block_threads(a.count * G);
@@ -1180,7 +1388,8 @@ hipError_t modexp(uint32_t k32, const ModexpArgs& a, hipStream_t st) {
     if (a.lo_bit) {   // split chains: head and tail at the caller's lanes, QS as the full chain's
       if (a.nadic) {   // the half-width N-adic head and the tail that takes over from it
         if (a.group != 16 || a.window != kNadicWindow || !a.state) return hipErrorInvalidValue;
-        return a.tail ? launch_modexp_tail<144, 16, 128, true, true>(a, st) : launch_modexp_nadic_head(a, st);
+        if (!a.tail) return launch_modexp_nadic_head(a, st);
+        return a.nadic_tail_full ? launch_modexp_tail<144, 16, 128, true, true>(a, st) : launch_modexp_nadic_tail(a, st);
       }
       switch (a.group) {
         case 16: return a.tail ? launch_modexp_tail<144, 16, 128, true>(a, st)

@@ -22,6 +22,7 @@ FSDKR_CFG_FB_BGMW = 2    # fixed-base exponentiations by BGMW windows only
 FSDKR_CFG_FB_COMB = 4    # a Lim-Lee comb wherever one fits
 FSDKR_CFG_INV_EACH = 8   # one inverse per element (no simultaneous inversion)
 FSDKR_CFG_GA_FULLWIDTH = 16   # GA's head as a generic 4096-bit chain (not half-width N-adic)
+FSDKR_CFG_GA_TAIL_FULLWIDTH = 32   # the N-adic head's tail at full width over its own tables
 
 u32p = ctypes.POINTER(ctypes.c_uint32)
 

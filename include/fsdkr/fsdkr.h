@@ -48,11 +48,15 @@ typedef struct fsdkr_cfg {
  *   FB_COMB   a Lim-Lee comb wherever one fits, even where it saves nothing
  *   INV_EACH  one binary-GCD inverse per element (no simultaneous inversion)
  *   GA_FULLWIDTH  the s^N mod N^2 chains of collect() run their head as a generic
- *             4096-bit Montgomery chain, not in half-width N-adic form */
+ *             4096-bit Montgomery chain, not in half-width N-adic form
+ *   GA_TAIL_FULLWIDTH  the N-adic head's joint tail converts the pair at its entry
+ *             and runs the low bits full width over tables of its own, not in
+ *             N-adic form over the head's table */
 #define FSDKR_CFG_FB_BGMW 2u
 #define FSDKR_CFG_FB_COMB 4u
 #define FSDKR_CFG_INV_EACH 8u
 #define FSDKR_CFG_GA_FULLWIDTH 16u
+#define FSDKR_CFG_GA_TAIL_FULLWIDTH 32u
 
 /* Context: owns the HIP stream, device buffers and per-modulus constant
  * tables.  Replaces nothing in the reference (which holds no state between
