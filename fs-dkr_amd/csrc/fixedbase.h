@@ -114,4 +114,24 @@ hipError_t launch_comb_sched(const CombSchedArgs& a, hipStream_t st);
 // fills the groups' block0 (blocks of the launch's size) and launches
 hipError_t launch_comb_exp(uint32_t k32, CombExpArgs& a, int group, hipStream_t st);
 
+// ---- constant-time two-base comb (comb_ct.hip): h1^x h2^y for secret x, y ---------
+// Tables of h = 4 (16 rows) per key and base, v_x / v_y blocks over a shared column
+// count b; instance i runs in block i / ipb, whose instances share key blk_key[block]
+// (the host orders by key and pads every key's run to whole blocks).
+constexpr int kCommitLanes = 4;
+struct CommitCtArgs {
+  const uint32_t* tabx;      // [n_keys][vx][16][KD]: h1's tables
+  const uint32_t* taby;      // [n_keys][vy][16][KD]: h2's tables
+  const uint16_t* sx;        // [blocks ipb][vx b] digits of x (comb_sched order), SECRET
+  const uint16_t* sy;        // [blocks ipb][vy b] digits of y, SECRET
+  const uint32_t* blk_key;   // [blocks]
+  const uint32_t* out_idx;   // [blocks ipb] output row (pads: a scratch row)
+  const uint32_t* consts;    // mod_setup rows of the keys' N~
+  uint32_t* out;             // rows of K32 limbs
+  uint32_t vx, vy, b, ipb, blocks;
+};
+// instances per block for a launch of `lanes` lanes in all (as comb_exp picks its block)
+uint32_t commit_ct_ipb(uint64_t lanes);
+hipError_t launch_commit_ct(uint32_t k32, const CommitCtArgs& a, hipStream_t st);
+
 }  // namespace fsdkr

@@ -66,6 +66,12 @@ class BobBatchC(ctypes.Structure):
                                     "s1", "s2", "t1", "t2", "X", "u")]
 
 
+class AliceBatchC(ctypes.Structure):
+    """struct fsdkr_alice_batch (include/fsdkr/fsdkr.h)."""
+    _fields_ = [(f, ctypes.c_uint32) for f in ("count", "n_keys", "nl", "el", "s1l", "s2l")] + \
+               [(f, u32p) for f in ("N", "Ntilde", "h1", "h2", "key_idx", "cipher", "z", "s", "e", "s1", "s2")]
+
+
 class RecoverJobC(ctypes.Structure):
     _fields_ = [("nl", ctypes.c_uint32), ("t_vss", ctypes.c_uint32), ("t_key", ctypes.c_uint32),
                 ("n_new", ctypes.c_uint32), ("old_index", u32p), ("cts", u32p), ("p", u32p), ("q", u32p),
@@ -156,6 +162,11 @@ def lib():
     L.fsdkr_mta_respond.restype = ctypes.c_int
     L.fsdkr_mta_respond_unfused.argtypes = L.fsdkr_mta_respond.argtypes
     L.fsdkr_mta_respond_unfused.restype = ctypes.c_int
+    L.fsdkr_alice_verify.argtypes = [vp, ctypes.POINTER(AliceBatchC), u8p]
+    L.fsdkr_alice_verify.restype = ctypes.c_int
+    L.fsdkr_pedersen_commit_ct.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p,
+                                           ctypes.c_uint32, u32p, u32p, u32p, u32p, ctypes.c_uint32, u32p]
+    L.fsdkr_pedersen_commit_ct.restype = ctypes.c_int
     L.fsdkr_modexp_batch_device.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, ctypes.c_uint32,
                                             ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp]
     L.fsdkr_modexp_batch_device.restype = ctypes.c_int
@@ -389,6 +400,15 @@ class Context:
         self.check(fn(self._h, ctypes.byref(batch), out.ctypes.data_as(u8p)))
         return out
 
+    def alice_verify(self, batch, count):
+        """fsdkr_alice_verify on a filled AliceBatchC -> uint8 verdicts (1 / 0); an empty
+        batch returns empty without a device call."""
+        out = np.zeros(count, dtype=np.uint8)
+        if count == 0:
+            return out
+        self.check(self._lib.fsdkr_alice_verify(self._h, ctypes.byref(batch), out.ctypes.data_as(u8p)))
+        return out
+
     def fixed_base_modexp(self, bases, base_mod_idx, mods, base_idx, exps, mod_limbs):
         """[bases[base_idx[i]] ^ exps[i] mod mods[base_mod_idx[base_idx[i]]]] via the fixed-base engine."""
         count = len(exps)
@@ -613,6 +633,31 @@ class Context:
         fn = self._lib.fsdkr_mta_respond if fused else self._lib.fsdkr_mta_respond_unfused
         self.check(fn(self._h, nl, count, _ptr(A), _ptr(B), _ptr(Bp), _ptr(Rr), _ptr(I), _ptr(Nn), len(ns), _ptr(O)))
         return limbs_to_ints(O[:count])
+
+    def pedersen_commit(self, xs, ys, keys, key_idx, nl, xl=None, yl=None):
+        """[h1^x h2^y mod N~] for (N~, h1, h2) = keys[key_idx[k]], x = xs[k], y = ys[k]
+        (fsdkr_pedersen_commit_ct): xs and ys are SECRET and run through the
+        constant-time comb.  xl / yl: limbs of the x / y rows, a PUBLIC bound that
+        alone sets the kernel's geometry (default: the widest value given, which
+        tells an observer of the launch that width)."""
+        count = len(xs)
+        if not (len(ys) == len(key_idx) == count):
+            raise ValueError("pedersen_commit: argument lists differ in length")
+        if count == 0:
+            return []
+        xl = xl or max(1, (max(v.bit_length() for v in xs) + 31) // 32)
+        yl = yl or max(1, (max(v.bit_length() for v in ys) + 31) // 32)
+        X, Y = ints_to_limbs(list(xs), xl), ints_to_limbs(list(ys), yl)
+        Nt, H1, H2 = (ints_to_limbs([k[c] for k in keys], nl) for c in range(3))
+        I = np.ascontiguousarray(np.asarray(key_idx, dtype=np.uint32))
+        O = np.zeros((count, nl), dtype=np.uint32)
+        try:
+            self.check(self._lib.fsdkr_pedersen_commit_ct(self._h, nl, count, _ptr(X), xl, _ptr(Y), yl, _ptr(I), _ptr(Nt),
+                                                          _ptr(H1), _ptr(H2), len(keys), _ptr(O)))
+        finally:
+            X.fill(0)
+            Y.fill(0)
+        return limbs_to_ints(O)
 
     def pdl_u1_check(self, s1s, es, Qs, u1s):
         """[G*(s1 mod q) + Q*(q - e mod q) == u1] per pair (uint8 0/1)."""

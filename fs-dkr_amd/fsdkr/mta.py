@@ -1,5 +1,16 @@
-"""Bob's MtA range proofs (range_proofs.rs:205-590) on the MI355X engine: the
-respondent's proofs of GG20's MtA (BobProof) and MtA with check (BobProofExt).
+"""GG20's MtA exchange (range_proofs.rs) on the MI355X engine: Alice's first
+message with its range proof (AliceProof, :26-203), the respondent's proofs
+(BobProof, BobProofExt, :205-590), Bob's response and Alice's decryption.
+
+initiate     Alice's first message for every exchange: c_A = Enc(a; r) in one
+             device call, then its proofs (generate_alice).
+generate_alice  the prover of AliceProof (AliceZkpRound1 / Round2, :40-96,
+             :168-202): the commitments z = h1^a h2^ro and w = h1^alpha h2^gamma of
+             ALL proofs in one call of the constant-time two-base comb
+             (Context.pedersen_commit, fsdkr_pedersen_commit_ct), u = Enc(alpha;
+             beta), s = r^e beta.
+verify_alice Bob's check of that message: AliceProof::verify (:112-164) of
+             `count` proofs in one device pass (fsdkr_alice_verify).
 
 verify_bob   `count` independent proofs in one device pass (fsdkr_bob_verify):
              the four h1 / h2 powers as fixed-base combs, z^e and t^e with one
@@ -22,7 +33,7 @@ import numpy as np
 from . import _native
 from .batch import UnsupportedInput, _limbs_for, pack, pack_points
 from .refresh import Q, FsDkrPanic, _ctx
-from .types import BobProof, BobProofExt
+from .types import AliceProof, BobProof, BobProofExt
 
 PANIC = 2          # verdict: the reference panics (X or u at infinity, range_proofs.rs:428-431)
 Q3 = Q ** 3
@@ -160,12 +171,183 @@ def verify_bob(proofs, a_encs, mta_outs, eks, statements, X=None, ctx=None, fuse
     return out
 
 
+def prepass_alice(proofs, ciphers, eks, statements):
+    """The host pre-pass of verify_alice: prepass without Bob's fields.  Returns
+    keys, key_idx, nl (the call's width class) and the proof fields with s1 clamped
+    to q^3 + 1 and e to 2^256 (the smallest values with their outcome)."""
+    count = len(proofs)
+    if not (len(ciphers) == len(eks) == len(statements) == count):
+        raise ValueError("verify_alice: argument lists differ in length")
+    for ek, st in zip(eks, statements):
+        for name, v in (("N", ek.n), ("Ntilde", st.N)):
+            if v <= 0 or v % 2 == 0:
+                raise UnsupportedInput(f"{name}: even, zero or negative modulus (the verifier's own key)")
+    keys, key_idx = key_table(eks, statements)
+    nl = width_class(eks, statements)
+    for name, col, limbs in (("N", 0, nl), ("Ntilde", 1, nl), ("h1", 2, nl), ("h2", 3, nl)):
+        _fits(name, [k[col] for k in keys], limbs)
+    _fits("cipher", ciphers, 2 * nl)
+    for f in ("z", "s"):
+        _fits(f, [getattr(p, f) for p in proofs], nl)
+    for f in ("e", "s1", "s2"):
+        if any(getattr(p, f) < 0 for p in proofs):
+            raise UnsupportedInput(f"{f}: negative value")
+    return {"count": count, "keys": keys, "key_idx": key_idx, "nl": nl, "s1": [min(p.s1, Q3 + 1) for p in proofs],
+            "e": [min(p.e, 1 << 256) for p in proofs], "s2": [p.s2 for p in proofs]}
+
+
+def _alice_batch(pp, ciphers, proofs):
+    count, nl = pp["count"], pp["nl"]
+    keep = []
+
+    def arr(values, limbs):
+        a = pack(list(values), limbs)
+        keep.append(a)
+        return a.ctypes.data_as(_u32p)
+
+    def width(values):
+        return _limbs_for(max(1, max(v.bit_length() for v in values)))
+
+    b = _native.AliceBatchC()
+    b.count, b.n_keys, b.nl = count, len(pp["keys"]), nl
+    b.el, b.s1l, b.s2l = width(pp["e"]), width(pp["s1"]), width(pp["s2"])
+    for col, name in enumerate(("N", "Ntilde", "h1", "h2")):
+        setattr(b, name, arr([k[col] for k in pp["keys"]], nl))
+    ki = np.ascontiguousarray(np.asarray(pp["key_idx"], dtype=np.uint32))
+    keep.append(ki)
+    b.key_idx = ki.ctypes.data_as(_u32p)
+    b.cipher = arr(ciphers, 2 * nl)
+    b.z, b.s = (arr([getattr(p, f) for p in proofs], nl) for f in ("z", "s"))
+    b.e, b.s1, b.s2 = arr(pp["e"], b.el), arr(pp["s1"], b.s1l), arr(pp["s2"], b.s2l)
+    return b, keep
+
+
+def verify_alice(proofs, ciphers, eks, statements, ctx=None):
+    """AliceProof::verify (range_proofs.rs:112-164) of every proof: Bob's check of
+    Alice's first MtA message ciphers[k] under her key eks[k], against his own
+    (N~, h1, h2) statements[k]; equal pairs share one row of the device's key table.
+
+    Returns np.uint8[count]: 1 accepted, 0 rejected (this path never panics).
+
+    Raises batch.UnsupportedInput as verify_bob does: a negative field; an even,
+    zero or negative N or N~; a key above 3072 bits; a hashed value wider than its
+    field in the call's width class (h1, h2, z, s above that width, cipher above
+    twice it)."""
+    proofs, ciphers, eks, statements = list(proofs), list(ciphers), list(eks), list(statements)
+    pp = prepass_alice(proofs, ciphers, eks, statements)
+    if pp["count"] == 0:
+        return np.zeros(0, dtype=np.uint8)
+    b, keep = _alice_batch(pp, ciphers, proofs)
+    out = _ctx(ctx).alice_verify(b, pp["count"])
+    del keep
+    return out
+
+
 def _from_modulo(rng, n):
     """SampleFromMultiplicativeGroup::from_modulo (range_proofs.rs:599-607)."""
     while True:
         r = rng.sample_below(n)
         if math.gcd(r, n) == 1:
             return r
+
+
+ALICE_XL = 24   # limbs of the comb's x rows: a < q and alpha < q^3 both run as 768-bit values
+
+
+def commit_yl(nl):
+    """Limbs of the comb's y rows in the width class nl: the public bound q^3 N~ of
+    gamma (ro < q N~ runs at the same width)."""
+    return ALICE_XL + nl
+
+
+def generate_alice(items, rng, ctx=None):
+    """AliceProof::generate (range_proofs.rs:168-202) for every item (a, cipher, ek,
+    statement, r): Alice's secret a in [0, 2^768), her ciphertext cipher = Enc(a; r)
+    under her key ek, the verifier's (N~, h1, h2) and the randomness r.
+
+    Per proof the draws go through `rng` (sample_below) in the reference's order
+    (:54-57): alpha, beta (from_modulo), gamma, ro.  The commitments z = h1^a h2^ro and
+    w = h1^alpha h2^gamma mod N~ of all proofs are ONE Context.pedersen_commit call (two
+    instances per proof, x rows of 24 limbs, y rows of commit_yl limbs: public bounds,
+    so the kernel's geometry tells nothing about the values); u = Enc(alpha; beta) runs
+    through Context.paillier_encrypt and s = r^e beta mod N through modexp_batch (e is
+    public).  Returns types.AliceProofs."""
+    ctx = _ctx(ctx)
+    items = list(items)
+    n = len(items)
+    if n == 0:
+        return []
+    for a, _, _, _, _ in items:
+        if a < 0 or a >> (32 * ALICE_XL):
+            raise ValueError("generate_alice: a must satisfy 0 <= a < 2^768")
+    eks, sts = [it[2] for it in items], [it[3] for it in items]
+    nl = width_class(eks, sts)
+    rnd = []
+    for a, cipher, ek, st, r in items:
+        alpha = rng.sample_below(Q3)
+        beta = _from_modulo(rng, ek.n)
+        gamma = rng.sample_below(Q3 * st.N)
+        ro = rng.sample_below(Q * st.N)
+        rnd.append((alpha, beta, gamma, ro))
+    keys, row = [], {}
+    for st in sts:
+        k = (st.N, st.g % st.N, st.ni % st.N)
+        if k not in row:
+            row[k] = len(keys)
+            keys.append(k)
+    xs, ys, idx = [], [], []
+    for (a, cipher, ek, st, r), (alpha, beta, gamma, ro) in zip(items, rnd):
+        k = row[(st.N, st.g % st.N, st.ni % st.N)]
+        xs += [a, alpha]
+        ys += [ro, gamma]
+        idx += [k, k]
+    zw = ctx.pedersen_commit(xs, ys, keys, idx, nl, xl=ALICE_XL, yl=commit_yl(nl))
+    ns, n_row = [], {}
+    for ek in eks:
+        if ek.n not in n_row:
+            n_row[ek.n] = len(ns)
+            ns.append(ek.n)
+    n_idx = [n_row[ek.n] for ek in eks]
+    us = ctx.paillier_encrypt([x[0] for x in rnd], [x[1] for x in rnd], ns, n_idx, nl)
+    from .distribute import chain_bigint
+    es = [chain_bigint(ek.n, ek.n + 1, it[1], zw[2 * k], us[k], zw[2 * k + 1]) for k, (it, ek) in enumerate(zip(items, eks))]
+    re = ctx.modexp_batch([it[4] % ek.n for it, ek in zip(items, eks)], es, ns, n_idx, nl)   # public e
+    out = []
+    for k, ((a, cipher, ek, st, r), (alpha, beta, gamma, ro)) in enumerate(zip(items, rnd)):
+        e = es[k]
+        out.append(AliceProof(zw[2 * k], e, re[k] * beta % ek.n, e * a + alpha, e * ro + gamma))
+    return out
+
+
+def initiate(as_, eks, statements, rng, ctx=None):
+    """Alice starts MtA (range_proofs.rs:650-670) for every exchange k: her secret
+    as_[k] (0 <= a < q), her own Paillier key eks[k] and Bob's (N~, h1, h2)
+    statements[k].
+
+    First, for every exchange in order, r_k = from_modulo(N_k) through `rng` (:656);
+    then ONE Context.paillier_encrypt call makes every c_A = Enc(a; r), at the width
+    class of the call's keys (width_class); then ONE generate_alice call over the same
+    rng proves them.  Returns (a_encs, rs, proofs)."""
+    ctx = _ctx(ctx)
+    as_, eks, statements = list(as_), list(eks), list(statements)
+    n = len(as_)
+    if not (len(eks) == len(statements) == n):
+        raise ValueError("initiate: argument lists differ in length")
+    for a in as_:
+        if a < 0 or a >= Q:
+            raise ValueError("initiate: a must satisfy 0 <= a < q")
+    if n == 0:
+        return [], [], []
+    nl = width_class(eks, statements)
+    rs = [_from_modulo(rng, ek.n) for ek in eks]
+    ns, n_row = [], {}
+    for ek in eks:
+        if ek.n not in n_row:
+            n_row[ek.n] = len(ns)
+            ns.append(ek.n)
+    a_encs = ctx.paillier_encrypt(as_, rs, ns, [n_row[ek.n] for ek in eks], nl)
+    proofs = generate_alice(list(zip(as_, a_encs, eks, statements, rs)), rng, ctx=ctx)
+    return a_encs, rs, proofs
 
 
 def _challenge(ek, a_enc, mta, z, z_prim, t, v, w, check):

@@ -423,6 +423,65 @@ int fsdkr_mta_respond_unfused(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, const
                               const uint32_t* beta_prim, const uint32_t* r, const uint32_t* n_idx,
                               const uint32_t* ns, uint32_t n_keys, uint32_t* out);
 
+/* ---- Alice's MtA range proof -------------------------------------------------
+ * AliceProof::verify (range_proofs.rs:112-164) of `count` independent proofs in one
+ * device pass: Bob's check of the first message of MtA, c_A = Enc(a; r) with its
+ * proof.  Laid out like fsdkr_bob_batch: a table of n_keys verifier keys (N odd,
+ * Ntilde odd, nl limbs; FSDKR_E_ARG otherwise), key_idx[p] the row of proof p, nl
+ * the batch's width class (64 or 96; any other FSDKR_E_UNSUPPORTED), narrower keys
+ * zero-extended.  Per proof, in the reference's order: s1 > q^3 rejects (s1 == q^3
+ * passes); z^e not a unit mod Ntilde rejects; cipher^e not a unit mod N^2 rejects;
+ * w = h1^s1 h2^s2 z^-e mod Ntilde; u = (1 + s1 N) s^N cipher^-e mod N^2; the hash
+ * of N, N + 1, cipher, z, u, w is compared with e.  Values at or above their
+ * modulus are reduced for the arithmetic and hashed as given; an e of 2^256 or
+ * more, or e == 0, rejects.  s^N cipher^-e runs as ONE split chain (the head over
+ * N's high bits, a two-base tail).  Lane rules are fsdkr_bob_verify's: at nl = 96 a
+ * context forced to a lane count other than 8 gets FSDKR_E_ARG, at nl = 64 other
+ * than 4, 8 or 16.  verdict[p]: 1 accepted, 0 rejected; this path never panics. */
+typedef struct fsdkr_alice_batch {
+  uint32_t count, n_keys, nl;
+  uint32_t el, s1l, s2l;    /* limbs of e, s1, s2 (el, s1l <= 64) */
+  const uint32_t* N;        /* [n_keys][nl]  alice_ek.n            */
+  const uint32_t* Ntilde;   /* [n_keys][nl]  dlog_statement.N      */
+  const uint32_t* h1;       /* [n_keys][nl]  dlog_statement.g      */
+  const uint32_t* h2;       /* [n_keys][nl]  dlog_statement.ni     */
+  const uint32_t* key_idx;  /* [count]                             */
+  const uint32_t* cipher;   /* [count][2nl]                        */
+  const uint32_t* z;        /* [count][nl]                         */
+  const uint32_t* s;        /* [count][nl]                         */
+  const uint32_t* e;        /* [count][el]                         */
+  const uint32_t* s1;       /* [count][s1l]                        */
+  const uint32_t* s2;       /* [count][s2l]                        */
+} fsdkr_alice_batch;
+
+int fsdkr_alice_verify(fsdkr_ctx* ctx, const fsdkr_alice_batch* batch, uint8_t* verdict);
+
+/* ---- Pedersen-style commitments with secret exponents -------------------------
+ * out[i] = h1^x[i] h2^y[i] mod Ntilde for the key key_idx[i]: the commitments of
+ * the range proofs (range_proofs.rs:58,62-63,270-295: z, w of AliceProof, z, z',
+ * t, w of BobProof) and of the PDL prover (zk_pdl_with_slack.rs:177-186), `count`
+ * of them in one device pass.  x and y are SECRET; Ntilde, h1 and h2 are public
+ * and belong to the verifier's key.  One constant-time Lim-Lee comb per commitment
+ * over both bases: tables of 16 rows per key and base, built once per call, every
+ * table read a masked scan of all 16 rows, b - 1 squarings and b (v_x + v_y)
+ * products with v = ceil(32 limbs / (4 b)).  The geometry comes from xl, yl and
+ * the instances per key alone: no value or bit length of x or y is looked at, and
+ * no address, branch or trip count on the device depends on them.  Before the
+ * call returns every device buffer that held x, y or their digit schedules is
+ * zeroed.  The host orders the instances by key and pads every key's run to whole
+ * blocks.
+ * nl = 64 or 96 (keys of up to 2048 / 3072 bits; a narrower key is zero-extended);
+ * any other nl: FSDKR_E_UNSUPPORTED.  1 <= xl, yl <= 128.  Ntilde odd and above 1,
+ * h1, h2 < Ntilde (refused, not reduced: they are public), key_idx in range: else
+ * FSDKR_E_ARG.  The comb runs at 4 lanes: a context forced to another lane count
+ * (fsdkr_ctx_set_modexp_group) gets FSDKR_E_ARG.  count == 0: OK. */
+int fsdkr_pedersen_commit_ct(fsdkr_ctx* ctx, uint32_t nl, uint32_t count,
+                             const uint32_t* x, uint32_t xl,   /* [count][xl] SECRET */
+                             const uint32_t* y, uint32_t yl,   /* [count][yl] SECRET */
+                             const uint32_t* key_idx,          /* [count] */
+                             const uint32_t* Ntilde, const uint32_t* h1, const uint32_t* h2, /* [n_keys][nl] */
+                             uint32_t n_keys, uint32_t* out);  /* [count][nl] */
+
 /* Which prestarted parts the last fsdkr_collect_prepare[_multi] reused (bit
  * mask): 1 GA chains, 2 fixed-base tables, 4 correct-key job, 8 ring-Pedersen
  * T^Z exponents (multi-session).  0 before any prepare.  Diagnostic (tests
