@@ -20,6 +20,7 @@
 // scratch row), so there is no bound check, the key's constants and tables are
 // addressed from a scalar load, and no address, branch or trip count depends on
 // x or y: the loop runs b (v_x + v_y) steps from the launch's limb counts.
+#include "commit_geom.hpp"
 #include "fixedbase.h"
 #include "mont29.hpp"
 
@@ -104,7 +105,7 @@ static hipError_t commit_launch(const CommitCtArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-uint32_t commit_ct_ipb(uint64_t lanes) { return lanes <= 256u * 4u * 64u ? 64u / kCommitLanes : (uint32_t)BLOCK / kCommitLanes; }
+static_assert(kCommitBlock == (uint32_t)BLOCK, "commit_ct_ipb's full block is the kernels' BLOCK");
 
 hipError_t launch_commit_ct(uint32_t k32, const CommitCtArgs& a, hipStream_t st) {
   if (!a.blocks) return hipSuccess;

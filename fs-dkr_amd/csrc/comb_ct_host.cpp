@@ -11,6 +11,7 @@
 #include <cstring>
 #include <vector>
 
+#include "commit_geom.hpp"
 #include "ctx.hpp"
 #include "fbjob.hpp"
 #include "fixedbase.h"
@@ -18,33 +19,6 @@
 #include "hostbn.hpp"
 #include "kernels.h"
 #include "mta_host.hpp"
-
-namespace fsdkr {
-
-// Column count b of the two-base comb with h = 4: the cheapest per commitment,
-//   (b - 1) + b (v_x + v_y) + (v_x + v_y) (11 + 4 b) / per_key
-// (squarings, products, and a key's eleven table products and 4 b chain squarings per
-// table shared by its instances), over 1 <= b <= 64 whose tables fit: a key's
-// (v_x + v_y) 16 rows within kCommitKeyBudget (they are re-read by every block of the
-// key, so they should stay in L2) and all keys' within `cap`.  0: nothing fits.
-constexpr size_t kCommitKeyBudget = (size_t)512 << 10;
-uint32_t commit_choose_b(uint32_t xl, uint32_t yl, double per_key, size_t n_keys, size_t entry_bytes, size_t cap) {
-  uint32_t best = 0;
-  double best_cost = 0.0;
-  for (uint32_t b = 1; b <= 64; ++b) {
-    const uint32_t vx = (8 * xl + b - 1) / b, vy = (8 * yl + b - 1) / b;
-    const size_t key_bytes = (size_t)(vx + vy) * 16 * entry_bytes;
-    if (key_bytes > kCommitKeyBudget || key_bytes * n_keys > cap) continue;
-    const double cost = (double)(b - 1) + (double)b * (vx + vy) + (double)(vx + vy) * (11.0 + 4.0 * b) / per_key;
-    if (!best || cost < best_cost) {
-      best = b;
-      best_cost = cost;
-    }
-  }
-  return best;
-}
-
-}  // namespace fsdkr
 
 using namespace fsdkr;
 
@@ -97,9 +71,7 @@ extern "C" int fsdkr_pedersen_commit_ct(fsdkr_ctx* ctx, uint32_t nl, uint32_t co
     return FSDKR_E_OOM;
   }
   const uint32_t vx = (8 * xl + b - 1) / b, vy = (8 * yl + b - 1) / b;
-  uint64_t lanes = 0;
-  for (uint32_t k = 0; k < nk; ++k) lanes += (uint64_t)((per[k] + 15) / 16 * 16) * kCommitLanes;
-  const uint32_t ipb = commit_ct_ipb(lanes);
+  const uint32_t ipb = commit_ct_ipb(commit_padded_lanes(per.data(), nk));
   // a key's run, padded to whole blocks; keys without instances take no block
   std::vector<uint32_t> start(nk + 1, 0u), blk_key;
   for (uint32_t k = 0; k < nk; ++k) {

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "commit_geom.hpp"
 #include "kernels.h"
 
 namespace fsdkr {
@@ -118,7 +119,6 @@ hipError_t launch_comb_exp(uint32_t k32, CombExpArgs& a, int group, hipStream_t 
 // Tables of h = 4 (16 rows) per key and base, v_x / v_y blocks over a shared column
 // count b; instance i runs in block i / ipb, whose instances share key blk_key[block]
 // (the host orders by key and pads every key's run to whole blocks).
-constexpr int kCommitLanes = 4;
 struct CommitCtArgs {
   const uint32_t* tabx;      // [n_keys][vx][16][KD]: h1's tables
   const uint32_t* taby;      // [n_keys][vy][16][KD]: h2's tables
@@ -130,8 +130,7 @@ struct CommitCtArgs {
   uint32_t* out;             // rows of K32 limbs
   uint32_t vx, vy, b, ipb, blocks;
 };
-// instances per block for a launch of `lanes` lanes in all (as comb_exp picks its block)
-uint32_t commit_ct_ipb(uint64_t lanes);
+// ipb is commit_ct_ipb's (commit_geom.hpp)
 hipError_t launch_commit_ct(uint32_t k32, const CommitCtArgs& a, hipStream_t st);
 
 }  // namespace fsdkr

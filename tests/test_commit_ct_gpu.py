@@ -1,9 +1,11 @@
 """GPU checks of the constant-time two-base comb (fsdkr_pedersen_commit_ct,
 csrc/comb_ct.hip): h1^x h2^y mod N~ against Python's pow bit for bit, on edge
 values of both exponents offset against each other and against three interleaved
-keys, at every width pair of the range proofs and at counts around the small
-launch's block (16 instances at 4 lanes) and the full block (64), with the key
-padding; and the error returns."""
+keys, at every width pair of the range proofs and at counts around one and four of
+the small launch's blocks (16 instances at 4 lanes: 15 / 16 / 17 and 63 / 64 / 65),
+with the key padding; and the error returns.  Every count here runs the small
+launch; the full block of 64 instances and the column counts of large batches are
+in tests/test_commit_ct_shapes_gpu.py."""
 import numpy as np
 import pytest
 
