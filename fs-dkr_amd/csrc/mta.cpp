@@ -6,6 +6,8 @@
 //   fsdkr_bob_verify_unfused    the same verdicts with three separate mod-N^2 chains (A/B)
 //   fsdkr_mta_respond           Bob's response a_enc^b (1 + beta' N) r^N mod N^2 (:688-704), see below
 //   fsdkr_mta_respond_unfused   the same values from separate chains and one product (A/B)
+//   fsdkr_bob_commit_v          the prover's v = a_enc^alpha (1 + gamma N) beta^N mod N^2 (:283-288)
+//   fsdkr_bob_commit_v_unfused  the same values from separate chains and one product (A/B)
 // Per proof, in the reference's order: s1 <= q^3 (:374); z^e, mta^e, t^e units
 // (:378-406); z' = h1^s1 h2^s2 z^-e, w = h1^t1 h2^t2 t^-e mod N~ (:385-388, :408-411);
 // v = a_enc^s1 s^N (1 + t1 N) mta^-e mod N^2 (:396-400); the transcript hash
@@ -529,11 +531,25 @@ int fsdkr_bob_verify_unfused(fsdkr_ctx* ctx, const fsdkr_bob_batch* batch, uint8
 // product.  Composed (nl = 96, or unfused): a_enc^b through the regular-access
 // modexp, r^N as fsdkr_paillier_encrypt runs it, and prod3 of the two with
 // 1 + beta' N; nothing returns to the host in between.
+//
+// The commitment v of Bob's range proof, a_enc^alpha (1 + gamma N) beta^N mod N^2
+// (range_proofs.rs:283-288), is the same computation with alpha < q^3 < 2^768 in b's
+// place: el = 24 limbs of secret exponent instead of 8, so the head stops at bit 768
+// and bob_v_tail_ct_kernel runs the rest; composed, a_enc^alpha is a 768-bit
+// regular-access modexp.  Its buffers have names of their own (other sizes).
 namespace {
 
+struct RespondNames {
+  const char *io, *table, *state, *t2, *ct, *mark;
+};
+constexpr RespondNames kRespNames{"resp_io", "mxt_resp", "mxt_resp_state", "mxt_resp_t2", "mxt_resp_ct", "mta_tail_ct"};
+constexpr RespondNames kBobVNames{"bobv_io", "mxt_bobv", "mxt_bobv_state", "mxt_bobv_t2", "mxt_bobv_ct", "bob_v_tail_ct"};
+
+// el: limbs per row of the secret exponent b, 8 (the response) or kBobVLimbs (v: alpha)
 int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const uint32_t* a_enc, const uint32_t* b,
                      const uint32_t* beta_prim, const uint32_t* r, const uint32_t* n_idx, const uint32_t* ns,
-                     uint32_t nk, uint32_t* out, bool want_fused) {
+                     uint32_t nk, uint32_t* out, bool want_fused, uint32_t el = 8) {
+  const RespondNames& nm = el == 8 ? kRespNames : kBobVNames;
   if (nl != 64 && nl != 96) {
     c->fail("%s: unsupported modulus width %u limbs", who, nl);
     return FSDKR_E_UNSUPPORTED;
@@ -609,11 +625,11 @@ int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const
     pad[k] = o >= count;
     row[k] = pad[k] ? row[k - 1] : o;   // a run's pads follow its chains
   }
-  const size_t o_a = take(n * rn), o_b = take(n * 32), o_bp = take(n64 * rl), o_np = take(n64 * 8);
+  const size_t o_a = take(n * rn), o_b = take(n * el * 4), o_bp = take(n64 * rl), o_np = take(n64 * 8);
   const size_t o_binom = take(n64 * rn), o_desc = take(J.desc_bytes()), o_out = take((C + 1) * rn);
   const size_t o_ab = take(fused ? 0 : C * rn), o_rn = take(fused ? 0 : C * rn), o_cdesc = take(fused ? 0 : C * 32);
   const size_t o_ops = take(fused ? 0 : C * sizeof(Prod3Operand)), o_midx = take(fused ? 0 : C * 4);
-  uint8_t* dev = (uint8_t*)c->buf("resp_io", off);
+  uint8_t* dev = (uint8_t*)c->buf(nm.io, off);
   if (!dev) {
     c->fail("%s: device allocation failed (%zu bytes)", who, off);
     return FSDKR_E_OOM;
@@ -624,14 +640,14 @@ int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const
     J.base_ptr[k] += (uint64_t)(uintptr_t)dev;
     J.exp_ptr[k] += (uint64_t)(uintptr_t)dev;
   }
-  std::vector<uint32_t> ha(n * nn), hb(n * 8, 0u), hbp(n64 * nl, 0u);
+  std::vector<uint32_t> ha(n * nn), hb(n * el, 0u), hbp(n64 * nl, 0u);
   std::vector<uint64_t> hnp(n64, DA(o_N));
   for (size_t k = 0; k < n; ++k) {
     const uint32_t p = row[k];
     memcpy(&ha[k * nn], a_enc + (size_t)p * nn, rn);
     hnp[k] = DA(o_N + n_idx[p] * rl);
     if (pad[k]) continue;   // b = 0, beta' = 0
-    memcpy(&hb[k * 8], b + (size_t)p * 8, 32);
+    memcpy(&hb[k * el], b + (size_t)p * el, el * 4);
     memcpy(&hbp[k * nl], beta_prim + (size_t)p * nl, rl);
   }
   std::vector<uint8_t> desc, cdesc;
@@ -639,9 +655,9 @@ int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const
   std::vector<Prod3Operand> ops;
   std::vector<uint32_t> midx;
   if (!fused) {
-    ModexpJob Jc;   // a_enc^b: 256-bit secret exponents
+    ModexpJob Jc;   // a_enc^b: secret exponents of 32 el bits
     Jc.k32 = nn;
-    for (uint32_t p = 0; p < count; ++p) Jc.add(DA(o_a + p * rn), nn, DA(o_b + (size_t)p * 32), 8, 256, n_idx[p]);
+    for (uint32_t p = 0; p < count; ++p) Jc.add(DA(o_a + p * rn), nn, DA(o_b + (size_t)p * el * 4), el, 32 * el, n_idx[p]);
     Jc.pack(cdesc);
     ops.resize(C);
     midx.assign(n_idx, n_idx + count);
@@ -655,7 +671,7 @@ int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const
   auto run = [&]() -> int {
     int rc;
     if ((rc = up(o_N, ns, nk * rl)) || (rc = up(o_NN, NN.data(), nk * rn)) || (rc = up(o_r, r, C * rl)) ||
-        (rc = up(o_a, ha.data(), n * rn)) || (rc = up(o_b, hb.data(), n * 32)) || (rc = up(o_bp, hbp.data(), n64 * rl)) ||
+        (rc = up(o_a, ha.data(), n * rn)) || (rc = up(o_b, hb.data(), n * el * 4)) || (rc = up(o_bp, hbp.data(), n64 * rl)) ||
         (rc = up(o_np, hnp.data(), n64 * 8)) || (rc = up(o_desc, desc.data(), desc.size())) ||
         (rc = up(o_cdesc, cdesc.data(), cdesc.size())) || (rc = up(o_ops, ops.data(), ops.size() * sizeof(Prod3Operand))) ||
         (rc = up(o_midx, midx.data(), midx.size() * 4)))
@@ -669,13 +685,13 @@ int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const
     if (rc) return rc;
     if (fused) {
       SplitArgs head;
-      head.lo_bit = kMtaTailLo;
-      if ((rc = launch_modexp_desc(c, nn, (uint32_t)n, nbits, dev + o_desc, cons, PU(o_out), st, "mxt_resp", 0, G, flags,
+      head.lo_bit = el == 8 ? kMtaTailLo : kBobVTailLo;   // 32 el: the secret exponent rides the tail
+      if ((rc = launch_modexp_desc(c, nn, (uint32_t)n, nbits, dev + o_desc, cons, PU(o_out), st, nm.table, 0, G, flags,
                                    &head)))
         return rc;
       const uint32_t w = choose_slide_window(nbits);   // the head's window (launch_modexp_desc)
-      const DevBuf tb = c->bufs["mxt_resp"], sb = c->bufs["mxt_resp_state"];
-      uint32_t* t2 = (uint32_t*)c->buf("mxt_resp_t2", n * 16 * 144 * 4);
+      const DevBuf tb = c->bufs[nm.table], sb = c->bufs[nm.state];
+      uint32_t* t2 = (uint32_t*)c->buf(nm.t2, n * 16 * 144 * 4);
       if (!tb.ptr || !sb.ptr || !t2) {
         c->fail("%s: device allocation failed (tail tables)", who);
         return FSDKR_E_OOM;
@@ -685,16 +701,16 @@ int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const
       MtaTailArgs ta{(const uint64_t*)(d + n8), (const uint32_t*)(d + 2 * n8 + 2 * n4), (const uint32_t*)(d + 2 * n8 + 4 * n4),
                      cons, (const uint32_t*)tb.ptr, (const uint32_t*)sb.ptr, w, PU(o_a), PU(o_b), PU(o_binom), t2,
                      PU(o_out), (uint32_t)n};
-      c->mark("mta_tail_ct", true);
-      rc = c->hip_check(launch_mta_tail_ct(ta, st), "mta_tail_ct");
-      c->mark("mta_tail_ct", false);
+      c->mark(nm.mark, true);
+      rc = c->hip_check(el == 8 ? launch_mta_tail_ct(ta, st) : launch_bob_v_tail_ct(ta, st), nm.mark);
+      c->mark(nm.mark, false);
       if (rc) return rc;
     } else {
       {
         CtScope ct(c);
-        if ((rc = launch_modexp_desc(c, nn, count, 256, dev + o_cdesc, cons, PU(o_ab), st, "mxt_resp_ct"))) return rc;
+        if ((rc = launch_modexp_desc(c, nn, count, 32 * el, dev + o_cdesc, cons, PU(o_ab), st, nm.ct))) return rc;
       }
-      if ((rc = launch_modexp_desc(c, nn, (uint32_t)J.size(), 32 * nl, dev + o_desc, cons, PU(o_rn), st, "mxt_resp", 0, G,
+      if ((rc = launch_modexp_desc(c, nn, (uint32_t)J.size(), 32 * nl, dev + o_desc, cons, PU(o_rn), st, nm.table, 0, G,
                                    flags)))
         return rc;
       Prod3Args pa{(const Prod3Operand*)(dev + o_ops), PU(o_midx), cons, PU(o_out), count};
@@ -709,7 +725,7 @@ int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const
   // scrub what held b, beta', r or a value made from them: the operand image, the
   // head's window table and state (powers of r), the regular-access table
   int rs = FSDKR_OK;
-  for (const char* name : {"resp_io", "mxt_resp", "mxt_resp_state", "mxt_resp_t2", "mxt_resp_ct"}) {
+  for (const char* name : {nm.io, nm.table, nm.state, nm.t2, nm.ct}) {
     const int q = scrub(c, name);
     if (!rs) rs = q;
   }
@@ -737,6 +753,24 @@ int fsdkr_mta_respond_unfused(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, const
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
   if (!c) return FSDKR_E_ARG;
   return mta_respond_impl(c, "fsdkr_mta_respond_unfused", nl, count, a_enc, b, beta_prim, r, n_idx, ns, n_keys, out, false);
+}
+
+int fsdkr_bob_commit_v(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, const uint32_t* a_enc, const uint32_t* alpha,
+                       const uint32_t* gamma, const uint32_t* beta, const uint32_t* n_idx, const uint32_t* ns,
+                       uint32_t n_keys, uint32_t* out) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return FSDKR_E_ARG;
+  return mta_respond_impl(c, "fsdkr_bob_commit_v", nl, count, a_enc, alpha, gamma, beta, n_idx, ns, n_keys, out, true,
+                          kBobVLimbs);
+}
+
+int fsdkr_bob_commit_v_unfused(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, const uint32_t* a_enc, const uint32_t* alpha,
+                               const uint32_t* gamma, const uint32_t* beta, const uint32_t* n_idx, const uint32_t* ns,
+                               uint32_t n_keys, uint32_t* out) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return FSDKR_E_ARG;
+  return mta_respond_impl(c, "fsdkr_bob_commit_v_unfused", nl, count, a_enc, alpha, gamma, beta, n_idx, ns, n_keys, out,
+                          false, kBobVLimbs);
 }
 
 }  // extern "C"

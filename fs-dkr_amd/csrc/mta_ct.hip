@@ -183,6 +183,145 @@ __global__ __launch_bounds__(64, 2) void mta_tail_ct_kernel(const MtaTailArgs a)
   for (int k = 0; k < LO; ++k) O[g * LO + k] = limb_full(stream, g * LO + k);
 }
 
+// The commitment v of Bob's range proof (range_proofs.rs:283-288),
+//   v = a_enc^alpha (1 + gamma N) beta^N mod N^2,
+// has the response's shape with alpha < q^3 < 2^768 in b's place, gamma mod N in
+// beta's and beta in r's: all three SECRET.  The head ran with lo_bit = 768, so this
+// tail runs 768 squarings: N's low 24 limbs in the scalar shift register, alpha as
+// 192 digits over T2.  alpha is not held in registers (24 VGPRs on top of the chain's
+// would spill): the limb in use is loaded from a.b[inst * 24 + k] once per 8 digits, k
+// the public loop counter, so the address depends on the instance and on k only.
+// Argument block, launch shape, regular access and the exit product's bound are
+// mta_tail_ct_kernel's (above); a.b has 24 limbs per row.
+// A kernel of its own: one body for both widths cost mta_tail_ct_kernel 6 VGPRs.
+__global__ __launch_bounds__(64, 2) void bob_v_tail_ct_kernel(const MtaTailArgs a) {
+  using MT = Mont29<KD, G>;
+  constexpr int STRIDE = cons_stride(KD);
+  constexpr int EL = (int)kBobVLimbs;
+  __shared__ uint32_t lds[WAVE_INST * KD];
+  const int g = threadIdx.x % G;
+  const int li = threadIdx.x / G;
+  const uint32_t inst = blockIdx.x * WAVE_INST + li;   // whole waves: no bound check
+  uint32_t* stream = lds + li * KD;
+  const uint32_t* C0 = a.consts + (size_t)a.mod_idx[inst] * STRIDE;   // N^2: the exit product
+  const uint32_t* C = C0 + cons_scaled(KD);                            // (N^2)': the chain's modulus
+  MT M;
+  M.init_lane(g);
+#pragma unroll
+  for (int j = 0; j < L; ++j) M.n[j] = C[g * L + j];
+  M.ninv = 1u;
+  const uint32_t w = a.window, tw = 1u << (w - 1);
+  const uint32_t* T = a.table + (size_t)inst * (tw + 1) * KD;
+  // N's bits below 2^768, wave-uniform, in a 24-limb scalar shift register
+  uint32_t nw[EL];
+  {
+    const uint32_t* E = reinterpret_cast<const uint32_t*>(a.exp_ptr[inst]);
+#pragma unroll
+    for (int k = 0; k < EL; ++k) nw[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)E[k]);
+  }
+  auto put_row = [&](const uint32_t* row) {
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < L; ++j) stream[g * L + j] = row[g * L + j];
+    __builtin_amdgcn_wave_barrier();
+  };
+  // T2[u] = a_enc^u (Montgomery form), u < 16
+  uint32_t* T2 = a.table2 + (size_t)inst * 16 * KD;
+  {
+    const uint32_t* A = a.a_enc + (size_t)inst * K32;
+    uint32_t y[L];
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+      y[j] = digit_full(A, g * L + j);
+      T2[g * L + j] = C[KD + g * L + j];   // T2[0] = 1 (R mod (N^2)')
+    }
+    put_row(C + 2 * KD);                   // R^2: y -> y R
+    M.mul_s(y, y, stream);
+#pragma unroll
+    for (int j = 0; j < L; ++j) T2[KD + g * L + j] = y[j];
+    __builtin_amdgcn_wave_barrier();
+    lds_put<KD, G>(stream, y, g);          // T2[1] streamed for the powers
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (int u = 2; u < 16; ++u) {
+      M.mul_s(y, y, stream);
+#pragma unroll
+      for (int j = 0; j < L; ++j) T2[(size_t)u * KD + g * L + j] = y[j];
+    }
+  }
+  const uint32_t* Al = a.b + (size_t)inst * EL;
+  uint32_t acc[L];
+#pragma unroll
+  for (int j = 0; j < L; ++j) acc[j] = a.state[(size_t)inst * KD + g * L + j];
+  // bits 767 .. 0, limb by limb of alpha: square; N's sliding windows multiply T[d >> 1]
+  // in after their last squaring; after every 4th squaring alpha's digit multiplies
+  // its T2 row in
+  uint32_t pend = 0, pend_d = 0;   // squarings until the open window's product (0: none), its odd digit
+#pragma unroll 1
+  for (int k = EL - 1; k >= 0; --k) {
+    asm volatile("" : "+s"(k));   // the limb counter stays on the scalar unit
+    uint32_t aw = Al[k];          // the 8 digits of this limb leave from the top
+#pragma unroll 1
+    for (int wi = 0; wi < 8; ++wi) {
+      asm volatile("" : "+s"(wi));
+#pragma unroll 1
+      for (int s = 0; s < 4; ++s) {
+        if (pend == 0 && (nw[EL - 1] >> 31)) {   // a window starts at this bit
+          const uint32_t top = nw[EL - 1] >> (32u - w);   // the next w bits (zeros below bit 0)
+          const uint32_t tz = (uint32_t)__builtin_ctz(top);
+          pend_d = top >> tz;
+          pend = w - tz;
+        }
+#pragma unroll
+        for (int q = EL - 1; q > 0; --q) nw[q] = (nw[q] << 1) | (nw[q - 1] >> 31);
+        nw[0] <<= 1;
+        __builtin_amdgcn_wave_barrier();
+        lds_put<KD, G>(stream, acc, g);
+        __builtin_amdgcn_wave_barrier();
+        M.sqr_s(acc, acc, stream);
+        if (pend != 0 && --pend == 0) {
+          put_row(T + (size_t)(pend_d >> 1) * KD);
+          M.mul_s(acc, acc, stream);
+        }
+      }
+      const uint32_t nib = aw >> 28;
+      aw <<= 4;
+      uint32_t row[L];
+      ct_row<L>(row, T2, nib, 16, KD, g);
+      __builtin_amdgcn_wave_barrier();
+      lds_put<KD, G>(stream, row, g);
+      __builtin_amdgcn_wave_barrier();
+      M.mul_s(acc, acc, stream);
+    }
+  }
+  // exit: acc (1 + gamma N) / R modulo N^2 itself.  The lane index is taken afresh,
+  // so the digit positions are worked out here and not carried along the chain in
+  // registers from a_enc's conversion
+  int ge = g;
+  asm volatile("" : "+v"(ge));
+  {
+    const uint32_t* Bn = a.binom + (size_t)inst * K32;
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+      M.n[j] = C0[ge * L + j];
+      stream[ge * L + j] = digit_full(Bn, ge * L + j);
+    }
+    M.ninv = C0[3 * KD];
+    __builtin_amdgcn_wave_barrier();
+  }
+  M.mul(acc, acc, stream);
+  M.carry_exact(acc);
+  M.sub_if_ge(acc);
+  __builtin_amdgcn_wave_barrier();
+  lds_put<KD, G>(stream, acc, g);
+  __builtin_amdgcn_wave_barrier();
+  uint32_t* O = a.out + (size_t)a.out_idx[inst] * K32;
+  constexpr int LO = K32 / G;
+#pragma unroll
+  for (int q = 0; q < LO; ++q) O[ge * LO + q] = limb_full(stream, ge * LO + q);
+}
+
 // out[p] = 1 + s[p] * n[p] for NL-limb factors (2 NL limbs out), one thread per row
 // of a launch of whole waves; every limb of s is multiplied in and every carry
 // runs to the top limb, so the instruction stream does not depend on s
@@ -218,6 +357,12 @@ __global__ __launch_bounds__(64) void binom_ct_kernel(const BinomCtArgs a) {
 hipError_t launch_mta_tail_ct(const MtaTailArgs& a, hipStream_t st) {
   if (!a.count_pad || a.count_pad % kMtaTailPad || a.window < 1 || a.window > 7) return hipErrorInvalidValue;
   hipLaunchKernelGGL(mta_tail_ct_kernel, dim3(a.count_pad / kMtaTailPad), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_bob_v_tail_ct(const MtaTailArgs& a, hipStream_t st) {
+  if (!a.count_pad || a.count_pad % kMtaTailPad || a.window < 1 || a.window > 7) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(bob_v_tail_ct_kernel, dim3(a.count_pad / kMtaTailPad), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 

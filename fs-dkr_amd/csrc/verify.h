@@ -187,9 +187,12 @@ struct EcMsmCtArgs {        // out[o] = sum_j scalars[o][j] * points[o][j]
 // no bound check: every per-instance array has count_pad rows, in launch order.
 constexpr uint32_t kMtaTailPad = 8;    // instances per wave
 constexpr uint32_t kMtaTailLo = 256;   // the head's lo_bit: b < 2^256 rides the tail
+// Bob's commitment v = a_enc^alpha (1 + gamma N) beta^N mod N^2: the same tail over
+// 768 squarings (bob_v_tail_ct_kernel), alpha < q^3 in b's place at 24 limbs per row
+constexpr uint32_t kBobVTailLo = 768, kBobVLimbs = 24;
 
 struct MtaTailArgs {
-  const uint64_t* exp_ptr;  // [count_pad] N's limbs (at least 8), shared by the instances of every wave
+  const uint64_t* exp_ptr;  // [count_pad] N's limbs (at least 8; bob_v: 24), shared by the instances of every wave
   const uint32_t* mod_idx;  // [count_pad] row of consts
   const uint32_t* out_idx;  // [count_pad] output row
   const uint32_t* consts;   // mod_setup rows of the 144-digit class (N^2 and its scaled block)
@@ -197,7 +200,7 @@ struct MtaTailArgs {
   const uint32_t* state;    // the head's accumulator [count_pad][144]
   uint32_t window;          // the head's sliding-window width
   const uint32_t* a_enc;    // [count_pad][128] reduced mod N^2 (public)
-  const uint32_t* b;        // [count_pad][8] SECRET
+  const uint32_t* b;        // [count_pad][8] SECRET (bob_v: alpha, [count_pad][24])
   const uint32_t* binom;    // [count_pad][128] 1 + beta' N (binom_ct_kernel) SECRET
   uint32_t* table2;         // [count_pad][16][144] scratch: a_enc^u
   uint32_t* out;            // rows of 128 limbs
@@ -212,6 +215,7 @@ struct BinomCtArgs {        // out = 1 + s * n for nl-limb factors, every limb o
 };
 
 hipError_t launch_mta_tail_ct(const MtaTailArgs& a, hipStream_t st);
+hipError_t launch_bob_v_tail_ct(const MtaTailArgs& a, hipStream_t st);
 hipError_t launch_binom_ct(uint32_t nl, const BinomCtArgs& a, hipStream_t st);   // nl = 64 or 96
 hipError_t launch_binom(const BinomArgs& a, hipStream_t st);
 hipError_t launch_ped_hash(const PedHashArgs& a, hipStream_t st);

@@ -162,6 +162,10 @@ def lib():
     L.fsdkr_mta_respond.restype = ctypes.c_int
     L.fsdkr_mta_respond_unfused.argtypes = L.fsdkr_mta_respond.argtypes
     L.fsdkr_mta_respond_unfused.restype = ctypes.c_int
+    L.fsdkr_bob_commit_v.argtypes = L.fsdkr_mta_respond.argtypes
+    L.fsdkr_bob_commit_v.restype = ctypes.c_int
+    L.fsdkr_bob_commit_v_unfused.argtypes = L.fsdkr_mta_respond.argtypes
+    L.fsdkr_bob_commit_v_unfused.restype = ctypes.c_int
     L.fsdkr_alice_verify.argtypes = [vp, ctypes.POINTER(AliceBatchC), u8p]
     L.fsdkr_alice_verify.restype = ctypes.c_int
     L.fsdkr_pedersen_commit_ct.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p,
@@ -632,6 +636,33 @@ class Context:
         O = np.zeros((max(1, count), 2 * nl), dtype=np.uint32)
         fn = self._lib.fsdkr_mta_respond if fused else self._lib.fsdkr_mta_respond_unfused
         self.check(fn(self._h, nl, count, _ptr(A), _ptr(B), _ptr(Bp), _ptr(Rr), _ptr(I), _ptr(Nn), len(ns), _ptr(O)))
+        return limbs_to_ints(O[:count])
+
+    def bob_commit_v(self, a_encs, alphas, gammas, betas, ns, n_idx, nl, fused=True):
+        """The commitment v of Bob's range proof [a_enc^alpha (1 + gamma N) beta^N mod N^2]
+        for N = ns[n_idx[k]] (range_proofs.rs:283-288; fsdkr_bob_commit_v).  alphas
+        (< 2^768, packed to 24 limbs), gammas (reduced below N) and betas (< N) are
+        SECRET and run in regular access; a_encs are reduced mod N^2.  ValueError for
+        a negative value or one wider than its row.
+        fused=False: the separate chains of fsdkr_bob_commit_v_unfused (A/B timing)."""
+        count = len(a_encs)
+        if not (len(alphas) == len(gammas) == len(betas) == len(n_idx) == count):
+            raise ValueError("bob_commit_v: argument lists differ in length")
+        Al = Ga = Be = None
+        try:
+            A = ints_to_limbs(list(a_encs), 2 * nl) if count else np.zeros((1, 2 * nl), dtype=np.uint32)
+            Al = ints_to_limbs(list(alphas), 24) if count else np.zeros((1, 24), dtype=np.uint32)
+            Ga = ints_to_limbs(list(gammas), nl) if count else np.zeros((1, nl), dtype=np.uint32)
+            Be = ints_to_limbs(list(betas), nl) if count else np.zeros((1, nl), dtype=np.uint32)
+            Nn = ints_to_limbs(list(ns), nl)
+            I = np.ascontiguousarray(np.asarray(list(n_idx) or [0], dtype=np.uint32))
+            O = np.zeros((max(1, count), 2 * nl), dtype=np.uint32)
+            fn = self._lib.fsdkr_bob_commit_v if fused else self._lib.fsdkr_bob_commit_v_unfused
+            self.check(fn(self._h, nl, count, _ptr(A), _ptr(Al), _ptr(Ga), _ptr(Be), _ptr(I), _ptr(Nn), len(ns), _ptr(O)))
+        finally:
+            for S in (Al, Ga, Be):
+                if S is not None:
+                    S.fill(0)
         return limbs_to_ints(O[:count])
 
     def pedersen_commit(self, xs, ys, keys, key_idx, nl, xl=None, yl=None):

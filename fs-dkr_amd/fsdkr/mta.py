@@ -20,7 +20,9 @@ verify_bob   `count` independent proofs in one device pass (fsdkr_bob_verify):
              class, keys of up to 3072 bits in the 96-limb class (one per call).
 generate_bob the prover (BobZkpRound1 / Round2, BobProof::generate), batched
              per round over the existing entry points; secret exponents run
-             through the regular-access kernel.
+             through the regular-access kernel, or with fused=True through the
+             constant-time comb (z, z', t, w: one Context.pedersen_commit call)
+             and one constant-time chain per v (Context.bob_commit_v).
 respond      Bob's side of one exchange ("Bob follows MtA", :688-704): the
              response mta_out = a_enc^b * Enc(beta'; r) on the device
              (fsdkr_mta_respond: one constant-time chain per response for keys of
@@ -361,7 +363,38 @@ def _challenge(ek, a_enc, mta, z, z_prim, t, v, w, check):
     return chain_bigint(*vals)
 
 
-def generate_bob(items, rng, ctx=None, check=False):
+BOB_XL_OVER = 16   # limbs of the comb's x rows above nl: gamma < q^2 N (b, alpha, beta' are narrower)
+
+
+def _bob_round1_fused(ctx, items, rnd, nl):
+    """z, z', t, w of every proof from ONE pedersen_commit call of four instances per
+    proof (xs = b, alpha, beta', gamma; ys = ro, ro', sigma, tau) at the public widths
+    xl = 16 + nl (gamma < q^2 N) and yl = commit_yl(nl) (tau, ro' < q^3 N~), and every
+    v from ONE bob_commit_v call over a_enc mod N^2, alpha, gamma mod N and beta.
+    Returns ([(z, z', t, w)], [v])."""
+    keys, row = [], {}
+    xs, ys, idx = [], [], []
+    for (a_enc, mta, b, beta_prim, ek, st, r), (alpha, beta, gamma, ro, ro_prim, sigma, tau) in zip(items, rnd):
+        k = (st.N, st.g % st.N, st.ni % st.N)
+        if k not in row:
+            row[k] = len(keys)
+            keys.append(k)
+        xs += [b, alpha, beta_prim, gamma]
+        ys += [ro, ro_prim, sigma, tau]
+        idx += [row[k]] * 4
+    cm = ctx.pedersen_commit(xs, ys, keys, idx, nl, xl=BOB_XL_OVER + nl, yl=commit_yl(nl))
+    ns, n_row = [], {}
+    for it in items:
+        if it[4].n not in n_row:
+            n_row[it[4].n] = len(ns)
+            ns.append(it[4].n)
+    vs = ctx.bob_commit_v([it[0] % it[4].nn for it in items], [x[0] for x in rnd],
+                          [x[2] % it[4].n for it, x in zip(items, rnd)], [x[1] for x in rnd], ns,
+                          [n_row[it[4].n] for it in items], nl)
+    return [tuple(cm[4 * k:4 * k + 4]) for k in range(len(items))], vs
+
+
+def generate_bob(items, rng, ctx=None, check=False, fused=False):
     """BobProof::generate (range_proofs.rs:448-515) / BobProofExt::generate
     (:564-589) for every item (a_enc, mta_out, b, beta_prim, ek, statement, r):
     Alice's ciphertext, the MtA output, Bob's secret scalar b in [0, q), the
@@ -371,12 +404,25 @@ def generate_bob(items, rng, ctx=None, check=False):
     alpha, beta (from_modulo), gamma, ro, ro_prim, sigma, tau (:266-272).  The
     exponentiations of all proofs are batched per round; every one with a secret
     exponent runs through the regular-access kernel, at the width class of the
-    call's keys (width_class).  Returns BobProofs, or BobProofExts with check=True."""
+    call's keys (width_class).  Returns BobProofs, or BobProofExts with check=True.
+
+    fused=True: the same draws and bit for bit the same proofs, with the four
+    commitments z, z', t, w of all proofs from ONE Context.pedersen_commit call (the
+    constant-time two-base comb, 4 n instances at public widths) and every v from ONE
+    Context.bob_commit_v call (fsdkr_bob_commit_v: one constant-time chain per v for
+    keys of up to 2048 bits); no regular-access modexp is issued.  It needs 0 <= b <
+    2^256 and 0 <= beta' < N (ValueError before any device call otherwise)."""
     ctx = _ctx(ctx)
     items = list(items)
     n = len(items)
     if n == 0:
         return []
+    if fused:
+        for a_enc, mta, b, beta_prim, ek, st, r in items:
+            if b < 0 or b >> 256:
+                raise ValueError("generate_bob: b must satisfy 0 <= b < 2^256")
+            if beta_prim < 0 or beta_prim >= ek.n:
+                raise ValueError("generate_bob: beta' must satisfy 0 <= beta' < N")
     nl = width_class([it[4] for it in items], [it[5] for it in items])
     rnd = []
     for a_enc, mta, b, beta_prim, ek, st, r in items:
@@ -389,6 +435,41 @@ def generate_bob(items, rng, ctx=None, check=False):
         tau = rng.sample_below(Q3 * st.N)
         rnd.append((alpha, beta, gamma, ro, ro_prim, sigma, tau))
     # round 1: h1^(b, alpha, beta', gamma), h2^(ro, ro', sigma, tau) mod N~; a_enc^alpha, beta^N mod N^2
+    if fused:
+        commits, vs = _bob_round1_fused(ctx, items, rnd, nl)
+    else:
+        commits, vs = _bob_round1_composed(ctx, items, rnd, nl)
+    pts = None
+    if check:   # X = G*b, u = G*alpha (:480-484): secret scalars, the constant-time comb
+        pts = ctx.ec_mul_g([it[2] % Q for it in items] + [x[0] % Q for x in rnd])
+    es, firsts = [], []
+    for k, ((a_enc, mta, b, beta_prim, ek, st, r), x) in enumerate(zip(items, rnd)):
+        z, z_prim, t, w = commits[k]
+        chk = (pts[k], pts[n + k]) if check else None
+        es.append(_challenge(ek, a_enc, mta, z, z_prim, t, vs[k], w, chk))
+        firsts.append((t, z))
+    # round 2: r^e mod N (:328)
+    ns, n_row = [], {}
+    for it in items:
+        if it[4].n not in n_row:
+            n_row[it[4].n] = len(ns)
+            ns.append(it[4].n)
+    re = ctx.modexp_batch([it[6] % it[4].n for it in items], es, ns, [n_row[it[4].n] for it in items], nl)   # public e
+    out = []
+    for k, ((a_enc, mta, b, beta_prim, ek, st, r), x) in enumerate(zip(items, rnd)):
+        alpha, beta, gamma, ro, ro_prim, sigma, tau = x
+        e = es[k]
+        t, z = firsts[k]
+        pf = BobProof(t, z, e, re[k] * beta % ek.n, e * b + alpha, e * ro + ro_prim, e * beta_prim + gamma,
+                      e * sigma + tau)
+        out.append(BobProofExt(pf, pts[n + k]) if check else pf)
+    return out
+
+
+def _bob_round1_composed(ctx, items, rnd, nl):
+    """z, z', t, w and v of every proof through the regular-access modexp: eight
+    powers mod N~ and a_enc^alpha mod N^2 per proof, beta^N with its public exponent,
+    the products on the host.  Returns ([(z, z', t, w)], [v])."""
     nts, nt_row = [], {}
     nns, nn_row = [], {}
     for _, _, _, _, ek, st, _ in items:
@@ -410,37 +491,15 @@ def generate_bob(items, rng, ctx=None, check=False):
                           [nn_row[it[4].nn] for it in items], 2 * nl, secret=True)
     bn = ctx.modexp_batch([x[1] for x in rnd], [it[4].n for it in items], nns, [nn_row[it[4].nn] for it in items],
                           2 * nl)   # beta^N: public exponent
-    pts = None
-    if check:   # X = G*b, u = G*alpha (:480-484): secret scalars, the constant-time comb
-        pts = ctx.ec_mul_g([it[2] % Q for it in items] + [x[0] % Q for x in rnd])
-    es, firsts = [], []
+    commits, vs = [], []
     for k, ((a_enc, mta, b, beta_prim, ek, st, r), x) in enumerate(zip(items, rnd)):
         p = pw[8 * k:8 * k + 8]
-        z, z_prim = p[0] * p[1] % st.N, p[2] * p[3] % st.N
-        t, w = p[4] * p[5] % st.N, p[6] * p[7] % st.N
-        v = va[k] * (x[2] * ek.n + 1) * bn[k] % ek.nn
-        chk = (pts[k], pts[n + k]) if check else None
-        es.append(_challenge(ek, a_enc, mta, z, z_prim, t, v, w, chk))
-        firsts.append((t, z))
-    # round 2: r^e mod N (:328)
-    ns, n_row = [], {}
-    for it in items:
-        if it[4].n not in n_row:
-            n_row[it[4].n] = len(ns)
-            ns.append(it[4].n)
-    re = ctx.modexp_batch([it[6] % it[4].n for it in items], es, ns, [n_row[it[4].n] for it in items], nl)   # public e
-    out = []
-    for k, ((a_enc, mta, b, beta_prim, ek, st, r), x) in enumerate(zip(items, rnd)):
-        alpha, beta, gamma, ro, ro_prim, sigma, tau = x
-        e = es[k]
-        t, z = firsts[k]
-        pf = BobProof(t, z, e, re[k] * beta % ek.n, e * b + alpha, e * ro + ro_prim, e * beta_prim + gamma,
-                      e * sigma + tau)
-        out.append(BobProofExt(pf, pts[n + k]) if check else pf)
-    return out
+        commits.append((p[0] * p[1] % st.N, p[2] * p[3] % st.N, p[4] * p[5] % st.N, p[6] * p[7] % st.N))
+        vs.append(va[k] * (x[2] * ek.n + 1) * bn[k] % ek.nn)
+    return commits, vs
 
 
-def respond(a_encs, bs, eks, statements, rng, ctx=None, check=False):
+def respond(a_encs, bs, eks, statements, rng, ctx=None, check=False, fused_proofs=False):
     """Bob follows MtA (range_proofs.rs:688-715) for every exchange k: Alice's
     ciphertext a_encs[k] under her key eks[k], Bob's secret scalar bs[k] (0 <= b <
     2^256) and Alice's (N~, h1, h2) statements[k].
@@ -453,7 +512,7 @@ def respond(a_encs, bs, eks, statements, rng, ctx=None, check=False):
 
     Returns (mta_outs, betas, proofs): the responses, Bob's additive shares
     beta = -beta' mod q, and BobProofs (check=True: BobProofExts, whose verifier
-    takes X = G*b)."""
+    takes X = G*b).  fused_proofs is generate_bob's `fused`."""
     ctx = _ctx(ctx)
     a_encs, bs, eks, statements = list(a_encs), list(bs), list(eks), list(statements)
     n = len(a_encs)
@@ -478,7 +537,7 @@ def respond(a_encs, bs, eks, statements, rng, ctx=None, check=False):
     mta_outs = ctx.mta_respond(a_red, bs, [d[0] for d in draws], [d[1] for d in draws], ns,
                                [n_row[ek.n] for ek in eks], nl)
     items = [(a, m, b, d[0], ek, st, d[1]) for a, m, b, d, ek, st in zip(a_encs, mta_outs, bs, draws, eks, statements)]
-    proofs = generate_bob(items, rng, ctx=ctx, check=check)
+    proofs = generate_bob(items, rng, ctx=ctx, check=check, fused=fused_proofs)
     return mta_outs, [(-d[0]) % Q for d in draws], proofs
 
 

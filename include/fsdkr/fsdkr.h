@@ -423,6 +423,39 @@ int fsdkr_mta_respond_unfused(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, const
                               const uint32_t* beta_prim, const uint32_t* r, const uint32_t* n_idx,
                               const uint32_t* ns, uint32_t n_keys, uint32_t* out);
 
+/* ---- The commitment v of Bob's range proof --------------------------------------
+ * BobZkpRound1 (range_proofs.rs:283-288): out = a_enc^alpha (1 + gamma N) beta^N mod N^2
+ * for `count` proofs in one device pass, N = ns[n_idx[i]] odd and above 1.  alpha
+ * (< q^3, any value below 2^768), gamma and beta are SECRET, with the guarantees of
+ * fsdkr_mta_respond: no address, branch or trip count on the device depends on them,
+ * and every device buffer that held one of them or a value made from them is zeroed
+ * before the call returns.  a_enc is public and must be reduced modulo N^2
+ * (FSDKR_E_ARG otherwise); gamma is given reduced below N (the prover's gamma < q^2 N
+ * enters v as gamma mod N) and beta below N: neither is checked, they are secret.
+ * nl = 64: ONE chain of bits(N) squarings per proof, the sliding-window head of beta^N
+ * over N's bits >= 768, then a constant-time joint tail of 768 squarings that carries
+ * a_enc^alpha along (192 fixed 4-bit digits, masked scans of all 16 rows) and
+ * multiplies 1 + gamma N in as it leaves Montgomery form.  Lanes as in
+ * fsdkr_mta_respond: a context forced to a lane count other than 8 gets FSDKR_E_ARG.
+ * nl = 96: a_enc^alpha through the regular-access kernel (768 bits), beta^N as
+ * fsdkr_paillier_encrypt runs it, and one modular product with 1 + gamma N.
+ * Any other nl: FSDKR_E_UNSUPPORTED.  Even N, N <= 1 or n_idx out of range:
+ * FSDKR_E_ARG.  count == 0: OK. */
+int fsdkr_bob_commit_v(fsdkr_ctx* ctx, uint32_t nl, uint32_t count,
+                       const uint32_t* a_enc,   /* [count][2nl], reduced mod N^2 by the caller */
+                       const uint32_t* alpha,   /* [count][24], any value < 2^768: SECRET */
+                       const uint32_t* gamma,   /* [count][nl], < N: SECRET */
+                       const uint32_t* beta,    /* [count][nl], < N: SECRET */
+                       const uint32_t* n_idx, const uint32_t* ns, uint32_t n_keys,
+                       uint32_t* out);          /* [count][2nl] */
+
+/* The same values with the separate chains and the product at nl = 64 as well: the
+ * A/B counterpart of fsdkr_bob_commit_v (tools/bench_bob_prover.py), not a second
+ * implementation to call.  It accepts any forced lane count. */
+int fsdkr_bob_commit_v_unfused(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, const uint32_t* a_enc,
+                               const uint32_t* alpha, const uint32_t* gamma, const uint32_t* beta,
+                               const uint32_t* n_idx, const uint32_t* ns, uint32_t n_keys, uint32_t* out);
+
 /* ---- Alice's MtA range proof -------------------------------------------------
  * AliceProof::verify (range_proofs.rs:112-164) of `count` independent proofs in one
  * device pass: Bob's check of the first message of MtA, c_A = Enc(a; r) with its
