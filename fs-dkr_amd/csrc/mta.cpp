@@ -524,19 +524,21 @@ int fsdkr_bob_verify_unfused(fsdkr_ctx* ctx, const fsdkr_bob_batch* batch, uint8
 // ---- Bob's MtA response --------------------------------------------------------
 // mta_out = Paillier::add(Paillier::mul(ek, a_enc, b), Enc(beta'; r))
 //         = a_enc^b (1 + beta' N) r^N mod N^2        (range_proofs.rs:688-704)
-// with b, beta' and r secret.  Fused (nl = 64): the head of r^N over N's bits >= 256
-// (modexp_slide_kernel: r is only the base; 16, 8 or 4 lanes by batch size), then
-// the 8-lane mta_tail_ct_kernel (mta_ct.hip), which carries a_enc^b along the last
+// with b, beta' and r secret.  Fused: the head of r^N over N's bits >= 256
+// (modexp_slide_kernel: r is only the base; nl = 64: 16, 8 or 4 lanes by batch size,
+// nl = 96: 8 lanes, the only 192-limb shape), then the 8-lane mta_tail_ct_kernel
+// (nl = 96: mta_tail_ct6144_kernel; mta_ct.hip), which carries a_enc^b along the last
 // 256 squarings in regular access and takes 1 + beta' N as the operand of its exit
-// product.  Composed (nl = 96, or unfused): a_enc^b through the regular-access
-// modexp, r^N as fsdkr_paillier_encrypt runs it, and prod3 of the two with
-// 1 + beta' N; nothing returns to the host in between.
+// product.  Composed (unfused, or nl = 96 with 4 or 16 lanes forced): a_enc^b through
+// the regular-access modexp, r^N as fsdkr_paillier_encrypt runs it, and prod3 of the
+// two with 1 + beta' N; nothing returns to the host in between.
 //
 // The commitment v of Bob's range proof, a_enc^alpha (1 + gamma N) beta^N mod N^2
 // (range_proofs.rs:283-288), is the same computation with alpha < q^3 < 2^768 in b's
 // place: el = 24 limbs of secret exponent instead of 8, so the head stops at bit 768
-// and bob_v_tail_ct_kernel runs the rest; composed, a_enc^alpha is a 768-bit
-// regular-access modexp.  Its buffers have names of their own (other sizes).
+// and bob_v_tail_ct_kernel (nl = 96: bob_v_tail_ct6144_kernel) runs the rest; composed,
+// a_enc^alpha is a 768-bit regular-access modexp.  Its buffers have names of their own
+// (other sizes).
 namespace {
 
 struct RespondNames {
@@ -560,7 +562,8 @@ int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const
     return FSDKR_E_ARG;
   }
   const uint32_t nn = 2 * nl;
-  const bool fused = want_fused && nl == 64;
+  // 192 limbs have the 8-lane head only: other forced lanes keep the composed path
+  const bool fused = want_fused && (nl == 64 || c->modexp_group == 0 || c->modexp_group == kMtaTailPad);
   if (fused && c->modexp_group != 0 && c->modexp_group != kMtaTailPad) {
     c->fail("%s: the fused chain runs at 8 lanes (forced %u)", who, c->modexp_group);
     return FSDKR_E_ARG;
@@ -601,11 +604,11 @@ int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const
           n_idx[p]);
   uint32_t G = 0, flags = 0;
   if (fused) {
-    // state and table rows are 144 digits in order whatever the lanes, so the head
-    // picks its lanes as the keyed launches do (a batch that leaves the chip half empty
-    // at 8 lanes runs 16) unless 8 are forced; the runs of one key are padded to whole
-    // waves of both kernels: 8 chains of the tail, 16 of a 4-lane head
-    G = c->modexp_group ? kMtaTailPad : keyed_lanes(count);
+    // state and table rows are the class's digits in order whatever the lanes, so at
+    // 128 limbs the head picks its lanes as the keyed launches do (a batch that leaves
+    // the chip half empty at 8 lanes runs 16) unless 8 are forced; the runs of one key
+    // are padded to whole waves of both kernels: 8 chains of the tail, 16 of a 4-lane head
+    G = (c->modexp_group || nl == 96) ? kMtaTailPad : keyed_lanes(count);
     if (!group_by_exponent(J, std::max(kMtaTailPad, 64 / G), count)) {
       c->fail("%s: instances not wave-uniform", who);
       return FSDKR_E_ARG;
@@ -691,7 +694,7 @@ int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const
         return rc;
       const uint32_t w = choose_slide_window(nbits);   // the head's window (launch_modexp_desc)
       const DevBuf tb = c->bufs[nm.table], sb = c->bufs[nm.state];
-      uint32_t* t2 = (uint32_t*)c->buf(nm.t2, n * 16 * 144 * 4);
+      uint32_t* t2 = (uint32_t*)c->buf(nm.t2, n * 16 * (size_t)shape_digits(nn) * 4);
       if (!tb.ptr || !sb.ptr || !t2) {
         c->fail("%s: device allocation failed (tail tables)", who);
         return FSDKR_E_OOM;
@@ -702,7 +705,9 @@ int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const
                      cons, (const uint32_t*)tb.ptr, (const uint32_t*)sb.ptr, w, PU(o_a), PU(o_b), PU(o_binom), t2,
                      PU(o_out), (uint32_t)n};
       c->mark(nm.mark, true);
-      rc = c->hip_check(el == 8 ? launch_mta_tail_ct(ta, st) : launch_bob_v_tail_ct(ta, st), nm.mark);
+      rc = c->hip_check(nl == 64 ? (el == 8 ? launch_mta_tail_ct(ta, st) : launch_bob_v_tail_ct(ta, st))
+                                 : (el == 8 ? launch_mta_tail_ct6144(ta, st) : launch_bob_v_tail_ct6144(ta, st)),
+                        nm.mark);
       c->mark(nm.mark, false);
       if (rc) return rc;
     } else {

@@ -26,6 +26,8 @@
 // addresses, and no address, branch or trip count depends on b, beta' or r.
 // binom_ct_kernel makes 1 + beta' N the same way (binom_kernel of vhash.hip skips
 // zero limbs of its factor: public factors only).
+// Keys of the 3072-bit class (N^2 < 2^6144) have tails of their own further down:
+// mta_tail_ct6144_kernel and bob_v_tail_ct6144_kernel.
 #include "mont29.hpp"
 #include "kernels.h"
 #include "verify.h"
@@ -37,19 +39,26 @@ namespace {
 constexpr int KD = 144, G = 8, K32 = 128, L = KD / G;
 constexpr int WAVE_INST = 64 / G;
 
-// digit j of a K32-limb integer: both limbs are always loaded, from an address
+// the 3072-bit class (mta_tail_ct6144_kernel, bob_v_tail_ct6144_kernel): the head's
+// Mont29<216, 8> rows, 27 digits per lane
+constexpr int KD6 = 216, K32_6 = 192, L6 = KD6 / G;
+
+// digit j of a KL-limb integer: both limbs are always loaded, from an address
 // clamped into the row, and masked where the digit lies past the top limb
+template <int KL = K32>
 __device__ __forceinline__ uint32_t digit_full(const uint32_t* __restrict__ x, int j) {
   const int bit = 29 * j;
   const int w = bit >> 5, sh = bit & 31;
-  const uint32_t m0 = 0u - (uint32_t)(w < K32), m1 = 0u - (uint32_t)(w + 1 < K32);
-  const uint32_t lo = x[min(w, K32 - 1)] & m0;
-  const uint32_t hi = x[min(w + 1, K32 - 1)] & m1;
+  const uint32_t m0 = 0u - (uint32_t)(w < KL), m1 = 0u - (uint32_t)(w + 1 < KL);
+  const uint32_t lo = x[min(w, KL - 1)] & m0;
+  const uint32_t hi = x[min(w + 1, KL - 1)] & m1;
   return (uint32_t)(mk64(lo, hi) >> sh) & M29;
 }
-// limb k < K32 of an exact-digit integer in LDS: 32 k / 29 + 2 < KD for every k
+// limb k < KL of an exact-digit integer in LDS: 32 k / 29 + 2 < DG for every k
+// (128 limbs: 142 < 144; 192 limbs: 212 < 216)
+template <int KL = K32, int DG = KD>
 __device__ __forceinline__ uint32_t limb_full(const uint32_t* d, int k) {
-  static_assert((32 * (K32 - 1)) / 29 + 2 < KD, "the three digits of every limb lie inside the row");
+  static_assert((32 * (KL - 1)) / 29 + 2 < DG, "the three digits of every limb lie inside the row");
   const int bit = 32 * k;
   const int j = bit / 29, sh = bit % 29;
   const uint64_t v = (uint64_t)d[j] | ((uint64_t)d[j + 1] << 29) | ((uint64_t)d[j + 2] << 58);
@@ -322,6 +331,165 @@ __global__ __launch_bounds__(64, 2) void bob_v_tail_ct_kernel(const MtaTailArgs 
   for (int q = 0; q < LO; ++q) O[ge * LO + q] = limb_full(stream, ge * LO + q);
 }
 
+// Both tails for the 3072-bit class: N^2 < 2^6144 at KD6 = 216 digits, 8 lanes of
+// L6 = 27, behind the head modexp_slide_kernel<216, 8, 192, true> (the only 192-limb
+// shape; state and table rows are its 216 digits in order).  EL = 8: the response,
+// 256 squarings; EL = kBobVLimbs: v, 768 squarings.  Argument block, launch shape
+// and regular access are mta_tail_ct_kernel's with 192-limb rows of a_enc, 1 + beta' N
+// and out, 216-word rows of consts, table, state and table2, and N's low EL limbs in
+// the scalar shift register.
+// The exit product's bound for R = 2^(29 * 216) = 2^6264: acc < 2 (N^2)',
+// (N^2)' < 2^29 N^2, 1 + beta' N < N^2 < 2^6144 and m < R give
+//   (acc (1 + beta' N) + m N^2) / R < N^2 (2^30 2^6144 / 2^6264 + 1) = N^2 (2^-90 + 1) < 2 N^2,
+// exact after carry_exact and one sub_if_ge.
+// Registers: 27 digits per lane make the squaring's 64-bit columns, the operand, its
+// doubled digits and the modulus 135 VGPRs, so what the 2048-bit kernels keep live
+// beside them does not fit here.  For both widths the secret exponent is read from
+// a.b[inst * EL + k] once per 8 digits (bob_v_tail_ct_kernel's way: the address
+// depends on the instance and the public counter k only), the head's accumulator is
+// loaded after the T2 build, and the lane index is taken afresh at the exit.  One
+// body serves both (nothing differs but EL), behind two plain kernels.
+namespace {
+
+template <int EL>
+__device__ __forceinline__ void tail_ct6144(const MtaTailArgs& a, uint32_t* lds) {
+  using MT = Mont29<KD6, G>;
+  constexpr int STRIDE = cons_stride(KD6);
+  const int g = threadIdx.x % G;
+  const int li = threadIdx.x / G;
+  const uint32_t inst = blockIdx.x * WAVE_INST + li;   // whole waves: no bound check
+  uint32_t* stream = lds + li * KD6;
+  const uint32_t* C0 = a.consts + (size_t)a.mod_idx[inst] * STRIDE;   // N^2: the exit product
+  const uint32_t* C = C0 + cons_scaled(KD6);                           // (N^2)': the chain's modulus
+  MT M;
+  M.init_lane(g);
+#pragma unroll
+  for (int j = 0; j < L6; ++j) M.n[j] = C[g * L6 + j];
+  M.ninv = 1u;
+  const uint32_t w = a.window, tw = 1u << (w - 1);
+  const uint32_t* T = a.table + (size_t)inst * (tw + 1) * KD6;
+  // N's bits below 2^(32 EL), wave-uniform, in an EL-limb scalar shift register
+  uint32_t nw[EL];
+  {
+    const uint32_t* E = reinterpret_cast<const uint32_t*>(a.exp_ptr[inst]);
+#pragma unroll
+    for (int k = 0; k < EL; ++k) nw[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)E[k]);
+  }
+  auto put_row = [&](const uint32_t* row) {
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < L6; ++j) stream[g * L6 + j] = row[g * L6 + j];
+    __builtin_amdgcn_wave_barrier();
+  };
+  // T2[u] = a_enc^u (Montgomery form), u < 16
+  uint32_t* T2 = a.table2 + (size_t)inst * 16 * KD6;
+  {
+    const uint32_t* A = a.a_enc + (size_t)inst * K32_6;
+    uint32_t y[L6];
+#pragma unroll
+    for (int j = 0; j < L6; ++j) {
+      y[j] = digit_full<K32_6>(A, g * L6 + j);
+      T2[g * L6 + j] = C[KD6 + g * L6 + j];   // T2[0] = 1 (R mod (N^2)')
+    }
+    put_row(C + 2 * KD6);                     // R^2: y -> y R
+    M.mul_s(y, y, stream);
+#pragma unroll
+    for (int j = 0; j < L6; ++j) T2[KD6 + g * L6 + j] = y[j];
+    __builtin_amdgcn_wave_barrier();
+    lds_put<KD6, G>(stream, y, g);            // T2[1] streamed for the powers
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (int u = 2; u < 16; ++u) {
+      M.mul_s(y, y, stream);
+#pragma unroll
+      for (int j = 0; j < L6; ++j) T2[(size_t)u * KD6 + g * L6 + j] = y[j];
+    }
+  }
+  const uint32_t* Bl = a.b + (size_t)inst * EL;
+  // the head's accumulator, taken after the T2 build: held across those products it
+  // went to scratch
+  uint32_t acc[L6];
+#pragma unroll
+  for (int j = 0; j < L6; ++j) acc[j] = a.state[(size_t)inst * KD6 + g * L6 + j];
+  // bits 32 EL - 1 .. 0, limb by limb of the secret exponent: square; N's sliding
+  // windows multiply T[d >> 1] in after their last squaring; after every 4th
+  // squaring the exponent's digit multiplies its T2 row in
+  uint32_t pend = 0, pend_d = 0;   // squarings until the open window's product (0: none), its odd digit
+#pragma unroll 1
+  for (int k = EL - 1; k >= 0; --k) {
+    asm volatile("" : "+s"(k));   // the limb counter stays on the scalar unit
+    uint32_t bw = Bl[k];          // the 8 digits of this limb leave from the top
+#pragma unroll 1
+    for (int wi = 0; wi < 8; ++wi) {
+      asm volatile("" : "+s"(wi));
+#pragma unroll 1
+      for (int s = 0; s < 4; ++s) {
+        if (pend == 0 && (nw[EL - 1] >> 31)) {   // a window starts at this bit
+          const uint32_t top = nw[EL - 1] >> (32u - w);   // the next w bits (zeros below bit 0)
+          const uint32_t tz = (uint32_t)__builtin_ctz(top);
+          pend_d = top >> tz;
+          pend = w - tz;
+        }
+#pragma unroll
+        for (int q = EL - 1; q > 0; --q) nw[q] = (nw[q] << 1) | (nw[q - 1] >> 31);
+        nw[0] <<= 1;
+        __builtin_amdgcn_wave_barrier();
+        lds_put<KD6, G>(stream, acc, g);
+        __builtin_amdgcn_wave_barrier();
+        M.sqr_s(acc, acc, stream);
+        if (pend != 0 && --pend == 0) {
+          put_row(T + (size_t)(pend_d >> 1) * KD6);
+          M.mul_s(acc, acc, stream);
+        }
+      }
+      const uint32_t nib = bw >> 28;
+      bw <<= 4;
+      uint32_t row[L6];
+      ct_row<L6>(row, T2, nib, 16, KD6, g);
+      __builtin_amdgcn_wave_barrier();
+      lds_put<KD6, G>(stream, row, g);
+      __builtin_amdgcn_wave_barrier();
+      M.mul_s(acc, acc, stream);
+    }
+  }
+  // exit: acc (1 + beta' N) / R modulo N^2 itself, the lane index taken afresh
+  int ge = g;
+  asm volatile("" : "+v"(ge));
+  {
+    const uint32_t* Bn = a.binom + (size_t)inst * K32_6;
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < L6; ++j) {
+      M.n[j] = C0[ge * L6 + j];
+      stream[ge * L6 + j] = digit_full<K32_6>(Bn, ge * L6 + j);
+    }
+    M.ninv = C0[3 * KD6];
+    __builtin_amdgcn_wave_barrier();
+  }
+  M.mul(acc, acc, stream);
+  M.carry_exact(acc);
+  M.sub_if_ge(acc);
+  __builtin_amdgcn_wave_barrier();
+  lds_put<KD6, G>(stream, acc, g);
+  __builtin_amdgcn_wave_barrier();
+  uint32_t* O = a.out + (size_t)a.out_idx[inst] * K32_6;
+  constexpr int LO = K32_6 / G;
+#pragma unroll
+  for (int q = 0; q < LO; ++q) O[ge * LO + q] = limb_full<K32_6, KD6>(stream, ge * LO + q);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(64, 2) void mta_tail_ct6144_kernel(const MtaTailArgs a) {
+  __shared__ uint32_t lds[WAVE_INST * KD6];
+  tail_ct6144<8>(a, lds);
+}
+
+__global__ __launch_bounds__(64, 2) void bob_v_tail_ct6144_kernel(const MtaTailArgs a) {
+  __shared__ uint32_t lds[WAVE_INST * KD6];
+  tail_ct6144<(int)kBobVLimbs>(a, lds);
+}
+
 // out[p] = 1 + s[p] * n[p] for NL-limb factors (2 NL limbs out), one thread per row
 // of a launch of whole waves; every limb of s is multiplied in and every carry
 // runs to the top limb, so the instruction stream does not depend on s
@@ -363,6 +531,18 @@ hipError_t launch_mta_tail_ct(const MtaTailArgs& a, hipStream_t st) {
 hipError_t launch_bob_v_tail_ct(const MtaTailArgs& a, hipStream_t st) {
   if (!a.count_pad || a.count_pad % kMtaTailPad || a.window < 1 || a.window > 7) return hipErrorInvalidValue;
   hipLaunchKernelGGL(bob_v_tail_ct_kernel, dim3(a.count_pad / kMtaTailPad), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_mta_tail_ct6144(const MtaTailArgs& a, hipStream_t st) {
+  if (!a.count_pad || a.count_pad % kMtaTailPad || a.window < 1 || a.window > 7) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mta_tail_ct6144_kernel, dim3(a.count_pad / kMtaTailPad), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_bob_v_tail_ct6144(const MtaTailArgs& a, hipStream_t st) {
+  if (!a.count_pad || a.count_pad % kMtaTailPad || a.window < 1 || a.window > 7) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(bob_v_tail_ct6144_kernel, dim3(a.count_pad / kMtaTailPad), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 

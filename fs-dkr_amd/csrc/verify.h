@@ -216,6 +216,9 @@ struct BinomCtArgs {        // out = 1 + s * n for nl-limb factors, every limb o
 
 hipError_t launch_mta_tail_ct(const MtaTailArgs& a, hipStream_t st);
 hipError_t launch_bob_v_tail_ct(const MtaTailArgs& a, hipStream_t st);
+// the same tails at 192 limbs (216-digit rows, 192-limb a_enc / binom / out)
+hipError_t launch_mta_tail_ct6144(const MtaTailArgs& a, hipStream_t st);
+hipError_t launch_bob_v_tail_ct6144(const MtaTailArgs& a, hipStream_t st);
 hipError_t launch_binom_ct(uint32_t nl, const BinomCtArgs& a, hipStream_t st);   // nl = 64 or 96
 hipError_t launch_binom(const BinomArgs& a, hipStream_t st);
 hipError_t launch_ped_hash(const PedHashArgs& a, hipStream_t st);

@@ -623,6 +623,7 @@ class Context:
         """Bob's MtA response [a_enc^b (1 + beta' N) r^N mod N^2] for N = ns[n_idx[k]]
         (range_proofs.rs:688-704; fsdkr_mta_respond).  bs (< 2^256), beta_prims and
         rs (< N) are SECRET and run in regular access; a_encs are reduced mod N^2.
+        nl = 64 and nl = 96 are one constant-time chain per response alike.
         fused=False: the separate chains of fsdkr_mta_respond_unfused (A/B timing)."""
         count = len(a_encs)
         if not (len(bs) == len(beta_prims) == len(rs) == len(n_idx) == count):
@@ -643,7 +644,8 @@ class Context:
         for N = ns[n_idx[k]] (range_proofs.rs:283-288; fsdkr_bob_commit_v).  alphas
         (< 2^768, packed to 24 limbs), gammas (reduced below N) and betas (< N) are
         SECRET and run in regular access; a_encs are reduced mod N^2.  ValueError for
-        a negative value or one wider than its row.
+        a negative value or one wider than its row.  nl = 64 and nl = 96 are one
+        constant-time chain per v alike.
         fused=False: the separate chains of fsdkr_bob_commit_v_unfused (A/B timing)."""
         count = len(a_encs)
         if not (len(alphas) == len(gammas) == len(betas) == len(n_idx) == count):

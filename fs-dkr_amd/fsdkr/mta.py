@@ -25,8 +25,8 @@ generate_bob the prover (BobZkpRound1 / Round2, BobProof::generate), batched
              and one constant-time chain per v (Context.bob_commit_v).
 respond      Bob's side of one exchange ("Bob follows MtA", :688-704): the
              response mta_out = a_enc^b * Enc(beta'; r) on the device
-             (fsdkr_mta_respond: one constant-time chain per response for keys of
-             up to 2048 bits), then its proofs (generate_bob).
+             (fsdkr_mta_respond: one constant-time chain per response in both
+             width classes), then its proofs (generate_bob).
 finish       Alice's last step: alpha = Dec(mta_out) mod q."""
 import math
 
@@ -409,8 +409,8 @@ def generate_bob(items, rng, ctx=None, check=False, fused=False):
     fused=True: the same draws and bit for bit the same proofs, with the four
     commitments z, z', t, w of all proofs from ONE Context.pedersen_commit call (the
     constant-time two-base comb, 4 n instances at public widths) and every v from ONE
-    Context.bob_commit_v call (fsdkr_bob_commit_v: one constant-time chain per v for
-    keys of up to 2048 bits); no regular-access modexp is issued.  It needs 0 <= b <
+    Context.bob_commit_v call (fsdkr_bob_commit_v: one constant-time chain per v in
+    both width classes); no regular-access modexp is issued.  It needs 0 <= b <
     2^256 and 0 <= beta' < N (ValueError before any device call otherwise)."""
     ctx = _ctx(ctx)
     items = list(items)

@@ -396,17 +396,19 @@ int fsdkr_bob_verify_unfused(fsdkr_ctx* ctx, const fsdkr_bob_batch* batch, uint8
  * made from r alone (the window table and state of the r^N chain), is zeroed.
  * a_enc is public and must be reduced modulo N^2 (FSDKR_E_ARG otherwise); b is any
  * value below 2^256; beta_prim and r are below N (not checked: they are secret).
- * nl = 64 (keys of up to 2048 bits): ONE chain of bits(N) squarings per response,
+ * nl = 64 (keys of up to 2048 bits) and nl = 96 (up to 3072 bits): ONE chain of
+ * bits(N) squarings per response,
  * the sliding-window head of r^N over N's bits >= 256, then a constant-time joint
  * tail that carries a_enc^b along the last 256 squarings (64 fixed 4-bit digits of
  * b, every table row read by a masked scan of all 16) and multiplies 1 + beta_prim N
  * in as it leaves Montgomery form.  The host orders and pads the instances so that
- * every wave holds one key.  The tail runs at 8 lanes (the head at 16, 8 or 4 by
- * batch size, at 8 when forced): a context forced to another lane count
- * (fsdkr_ctx_set_modexp_group) gets FSDKR_E_ARG.
- * nl = 96 (up to 3072 bits): the same values from separate chains (a_enc^b through
- * the regular-access kernel of fsdkr_modexp_batch_ct, r^N as fsdkr_paillier_encrypt
- * runs it) and one modular product on the device.
+ * every wave holds one key.  The tail runs at 8 lanes.  nl = 64: the head runs at
+ * 16, 8 or 4 lanes by batch size, at 8 when forced, and a context forced to another
+ * lane count (fsdkr_ctx_set_modexp_group) gets FSDKR_E_ARG.  nl = 96: head and tail
+ * run at 8 lanes, and a context forced to another lane count gets the same values
+ * from separate chains (a_enc^b through the regular-access kernel of
+ * fsdkr_modexp_batch_ct, r^N as fsdkr_paillier_encrypt runs it) and one modular
+ * product on the device.
  * Any other nl: FSDKR_E_UNSUPPORTED.  Even N or N <= 1: FSDKR_E_ARG.  count == 0: OK. */
 int fsdkr_mta_respond(fsdkr_ctx* ctx, uint32_t nl, uint32_t count,
                       const uint32_t* a_enc,      /* [count][2nl], reduced mod N^2 by the caller */
@@ -416,7 +418,7 @@ int fsdkr_mta_respond(fsdkr_ctx* ctx, uint32_t nl, uint32_t count,
                       const uint32_t* n_idx, const uint32_t* ns, uint32_t n_keys,
                       uint32_t* out);             /* [count][2nl] */
 
-/* The same values with the separate chains and the product at nl = 64 as well: the
+/* The same values with the separate chains and the product at both widths: the
  * A/B counterpart of fsdkr_mta_respond (tools/bench_mta_respond.py), not a second
  * implementation to call.  It accepts any forced lane count. */
 int fsdkr_mta_respond_unfused(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, const uint32_t* a_enc, const uint32_t* b,
@@ -432,13 +434,15 @@ int fsdkr_mta_respond_unfused(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, const
  * before the call returns.  a_enc is public and must be reduced modulo N^2
  * (FSDKR_E_ARG otherwise); gamma is given reduced below N (the prover's gamma < q^2 N
  * enters v as gamma mod N) and beta below N: neither is checked, they are secret.
- * nl = 64: ONE chain of bits(N) squarings per proof, the sliding-window head of beta^N
+ * nl = 64 and nl = 96: ONE chain of bits(N) squarings per proof, the sliding-window
+ * head of beta^N
  * over N's bits >= 768, then a constant-time joint tail of 768 squarings that carries
  * a_enc^alpha along (192 fixed 4-bit digits, masked scans of all 16 rows) and
  * multiplies 1 + gamma N in as it leaves Montgomery form.  Lanes as in
- * fsdkr_mta_respond: a context forced to a lane count other than 8 gets FSDKR_E_ARG.
- * nl = 96: a_enc^alpha through the regular-access kernel (768 bits), beta^N as
- * fsdkr_paillier_encrypt runs it, and one modular product with 1 + gamma N.
+ * fsdkr_mta_respond: at nl = 64 a context forced to a lane count other than 8 gets
+ * FSDKR_E_ARG; at nl = 96 it gets the same values from a_enc^alpha through the
+ * regular-access kernel (768 bits), beta^N as fsdkr_paillier_encrypt runs it, and one
+ * modular product with 1 + gamma N.
  * Any other nl: FSDKR_E_UNSUPPORTED.  Even N, N <= 1 or n_idx out of range:
  * FSDKR_E_ARG.  count == 0: OK. */
 int fsdkr_bob_commit_v(fsdkr_ctx* ctx, uint32_t nl, uint32_t count,
@@ -449,7 +453,7 @@ int fsdkr_bob_commit_v(fsdkr_ctx* ctx, uint32_t nl, uint32_t count,
                        const uint32_t* n_idx, const uint32_t* ns, uint32_t n_keys,
                        uint32_t* out);          /* [count][2nl] */
 
-/* The same values with the separate chains and the product at nl = 64 as well: the
+/* The same values with the separate chains and the product at both widths: the
  * A/B counterpart of fsdkr_bob_commit_v (tools/bench_bob_prover.py), not a second
  * implementation to call.  It accepts any forced lane count. */
 int fsdkr_bob_commit_v_unfused(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, const uint32_t* a_enc,

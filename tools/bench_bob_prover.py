@@ -1,7 +1,7 @@
 """Bob's MtA prover on the constant-time entries against the composed paths, in one
 process on the same inputs:
 
-  (a) fsdkr_bob_commit_v (at 2048 bits ONE chain of bits(N) squarings per v: the
+  (a) fsdkr_bob_commit_v (ONE chain of bits(N) squarings per v: the
       sliding-window head of beta^N, then the 768-squaring constant-time joint tail)
       against fsdkr_bob_commit_v_unfused (a_enc^alpha through the regular-access
       modexp, beta^N as fsdkr_paillier_encrypt runs it, one prod3), `--count`
@@ -12,9 +12,8 @@ process on the same inputs:
       one key and `--keys` proofs under `--keys` keys; wall time of the whole Python
       call, draws and packing included (the same for both paths).
 
-At `--bits 3072` both entries of (a) run the composed path (the fused 6144-bit
-shape does not exist), so that run shows the noise of the comparison itself; (b)
-still differs by the comb.  The moduli are random odd values of full width (the
+`--bits 3072` runs the 6144-bit chain of (a): both width classes have the fused
+shape, and (b) differs by it and by the comb.  The moduli are random odd values of full width (the
 device's work does not depend on their factors); the batch of (a) is `--distinct`
 instances repeated.  Both paths must agree (with pow for (a), with each other for
 (b)) before anything is timed.  Per path: `--warmup` calls, then `--reps` timed calls,

@@ -1,11 +1,10 @@
-"""Bob's MtA response, responses/s: fsdkr_mta_respond (at 2048 bits ONE chain of
-bits(N) squarings per response: the sliding-window head of r^N, then the
-constant-time joint tail that carries a_enc^b and takes 1 + beta' N at its exit)
+"""Bob's MtA response, responses/s: fsdkr_mta_respond (ONE chain of bits(N)
+squarings per response: the sliding-window head of r^N, then the constant-time
+joint tail that carries a_enc^b and takes 1 + beta' N at its exit)
 against fsdkr_mta_respond_unfused (a_enc^b through the regular-access modexp, r^N
 as fsdkr_paillier_encrypt runs it, one prod3), in one process, on the same packed
-batch of `--count` responses under one key of `--bits` 2048 or 3072.  At 3072 bits
-both entries run the composed path (the fused 6144-bit shape does not exist), so
-that run shows the noise of the comparison itself.
+batch of `--count` responses under one key of `--bits` 2048 or 3072 (the 4096-bit
+or the 6144-bit chain: both width classes have the fused shape).
 
 The batch is `--distinct` exchanges (random a_enc, b, beta', r) repeated to
 `--count`: the device's work per response does not depend on the values.  Both
