@@ -28,7 +28,14 @@ extern "C" int fsdkr_pedersen_commit_ct(fsdkr_ctx* ctx, uint32_t nl, uint32_t co
                                         uint32_t n_keys, uint32_t* out) {
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
   if (!c) return FSDKR_E_ARG;
-  const char* who = "fsdkr_pedersen_commit_ct";
+  return pedersen_commit_ct_run(c, "fsdkr_pedersen_commit_ct", nl, count, x, xl, y, yl, key_idx, Ntilde, h1, h2, n_keys,
+                                out);
+}
+
+// the whole stage, shared with the provers of mta_prove.cpp (mta_host.hpp)
+int fsdkr::pedersen_commit_ct_run(Ctx* c, const char* who, uint32_t nl, uint32_t count, const uint32_t* x, uint32_t xl,
+                                  const uint32_t* y, uint32_t yl, const uint32_t* key_idx, const uint32_t* Ntilde,
+                                  const uint32_t* h1, const uint32_t* h2, uint32_t n_keys, uint32_t* out) {
   if (nl != 64 && nl != 96) {
     c->fail("%s: unsupported modulus width %u limbs", who, nl);
     return FSDKR_E_UNSUPPORTED;

@@ -547,10 +547,13 @@ struct RespondNames {
 constexpr RespondNames kRespNames{"resp_io", "mxt_resp", "mxt_resp_state", "mxt_resp_t2", "mxt_resp_ct", "mta_tail_ct"};
 constexpr RespondNames kBobVNames{"bobv_io", "mxt_bobv", "mxt_bobv_state", "mxt_bobv_t2", "mxt_bobv_ct", "bob_v_tail_ct"};
 
-// el: limbs per row of the secret exponent b, 8 (the response) or kBobVLimbs (v: alpha)
-int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const uint32_t* a_enc, const uint32_t* b,
-                     const uint32_t* beta_prim, const uint32_t* r, const uint32_t* n_idx, const uint32_t* ns,
-                     uint32_t nk, uint32_t* out, bool want_fused, uint32_t el = 8) {
+}  // namespace
+
+// el: limbs per row of the secret exponent b, 8 (the response) or kBobVLimbs (v: alpha);
+// shared with the provers of mta_prove.cpp (mta_host.hpp)
+int fsdkr::mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const uint32_t* a_enc,
+                            const uint32_t* b, const uint32_t* beta_prim, const uint32_t* r, const uint32_t* n_idx,
+                            const uint32_t* ns, uint32_t nk, uint32_t* out, bool want_fused, uint32_t el) {
   const RespondNames& nm = el == 8 ? kRespNames : kBobVNames;
   if (nl != 64 && nl != 96) {
     c->fail("%s: unsupported modulus width %u limbs", who, nl);
@@ -739,8 +742,6 @@ int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const
   wipe(hbp);
   return rc ? rc : rs ? rs : ry;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -75,6 +75,18 @@ inline void inverse_groups(const uint32_t* key, uint32_t reps, uint32_t count, u
     }
 }
 
+// Whole device stages that more than one entry point runs.  Each uploads its rows,
+// runs, copies its (public) results to `out` on the host, scrubs what held a secret
+// and synchronises; `who` names the entry in error messages.
+// fsdkr_pedersen_commit_ct (comb_ct_host.cpp)
+int pedersen_commit_ct_run(Ctx* c, const char* who, uint32_t nl, uint32_t count, const uint32_t* x, uint32_t xl,
+                           const uint32_t* y, uint32_t yl, const uint32_t* key_idx, const uint32_t* Ntilde,
+                           const uint32_t* h1, const uint32_t* h2, uint32_t n_keys, uint32_t* out);
+// fsdkr_mta_respond (el = 8) and fsdkr_bob_commit_v (el = kBobVLimbs) (mta.cpp)
+int mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count, const uint32_t* a_enc, const uint32_t* b,
+                     const uint32_t* beta_prim, const uint32_t* r, const uint32_t* n_idx, const uint32_t* ns,
+                     uint32_t nk, uint32_t* out, bool want_fused, uint32_t el = 8);
+
 // lanes per chain of the split launch: a forced context setting (tests, tuning)
 // where the tail has that shape, else by batch size; 192-limb moduli: 8 lanes
 inline int split_group(Ctx* c, const char* who, uint32_t count, bool wide_ok, uint32_t k32, uint32_t* group) {

@@ -214,6 +214,23 @@ struct BinomCtArgs {        // out = 1 + s * n for nl-limb factors, every limb o
   uint32_t count_pad;       // a multiple of 64
 };
 
+// The provers' integer responses (resp_ct.hip): out = e * x + y over 32-bit limbs, no
+// modulus, e public (8 limbs), x and y SECRET.  Whole blocks of kRespPad instances,
+// no bound check: every array has count_pad rows.
+struct RespCtArgs {
+  const uint32_t* e;        // [count_pad][8]
+  const uint32_t* x;        // [count_pad][xl] SECRET
+  const uint32_t* y;        // [count_pad][yl] SECRET
+  uint32_t* out;            // [count_pad][ol]
+  uint32_t xl, yl, ol;      // 1 <= xl, yl <= 128; ol = resp_out_limbs(xl, yl)
+  uint32_t count_pad;       // a multiple of kRespPad
+};
+hipError_t launch_resp_ct(const RespCtArgs& a, hipStream_t st);
+// the provers' challenges: the transcripts of bob_hash / alice_hash, written as 8
+// little-endian limbs per proof instead of compared (a.e, a.verdict are not read)
+hipError_t launch_bob_challenge(const BobHashArgs& a, uint32_t* e_out, hipStream_t st);
+hipError_t launch_alice_challenge(const AliceHashArgs& a, uint32_t* e_out, hipStream_t st);
+
 hipError_t launch_mta_tail_ct(const MtaTailArgs& a, hipStream_t st);
 hipError_t launch_bob_v_tail_ct(const MtaTailArgs& a, hipStream_t st);
 // the same tails at 192 limbs (216-digit rows, 192-limb a_enc / binom / out)

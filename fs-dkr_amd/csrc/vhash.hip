@@ -4,6 +4,9 @@
 //   (the PDL challenge e = H(G,Q,c,z,u1,u2,u3), zk_pdl_with_slack.rs:114-122, is
 //    hashed on the host by fsdkr_collect_prepare: collect.cpp)
 //   alice_hash      e' = H(N,N+1,c,z,u,w) == e                 range_proofs.rs:150-163
+//   bob_hash        e' = H(N,N+1,a_enc,mta,z,z',t,v,w[,X,u]) == e   range_proofs.rs:413-441
+//   alice_challenge, bob_challenge   the same transcripts, e written out (the provers
+//                   of mta_prove.cpp; alice_digest / bob_digest are shared with the above)
 //   ped_hash        e = H(A_0..A_M-1), Lsb0 bits              ring_pedersen_proof.rs:130-142
 //   binom           (N+1)^s1 = 1 + s1*N  (s1 < N)              zk_pdl_with_slack.rs:129-135
 #include "mont29.hpp"
@@ -204,14 +207,9 @@ __global__ void alice_prefix_kernel(const AliceHashArgs a) {
   for (int i = 0; i < 16; ++i) s[11 + i] = h.w[i];
 }
 
-// e' = H(N, N+1, c, z, u, w) == e  ->  verdict bit (AND-ed with the host's pre-checks);
-// with a.state the prefix comes from alice_prefix_kernel
-__global__ void alice_hash_kernel(const AliceHashArgs a) {
-  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= a.count) return;
-  __shared__ uint32_t sha_w[64 * 16];  // launch blocks are 64 threads
-  Sha256 h;
-  h.init(sha_w + threadIdx.x * 16);
+// the digest of Alice's transcript H(N, N+1, c, z, u, w) as 8 little-endian limbs (h
+// initialised by the caller); with a.state the prefix comes from alice_prefix_kernel
+__device__ __forceinline__ void alice_digest(Sha256& h, const AliceHashArgs& a, uint32_t p, uint32_t* d) {
   if (a.state) {
     const uint32_t* s = a.state + (size_t)p * 32;
 #pragma unroll
@@ -225,8 +223,18 @@ __global__ void alice_hash_kernel(const AliceHashArgs a) {
   }
   h.bigint(a.u + (size_t)p * a.c_len, a.c_len);
   h.bigint(a.w + (size_t)p * a.z_len, a.z_len);
-  uint32_t d[8];
   h.finish_le(d);
+}
+
+// e' = H(N, N+1, c, z, u, w) == e  ->  verdict bit (AND-ed with the host's pre-checks)
+__global__ void alice_hash_kernel(const AliceHashArgs a) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= a.count) return;
+  __shared__ uint32_t sha_w[64 * 16];  // launch blocks are 64 threads
+  Sha256 h;
+  h.init(sha_w + threadIdx.x * 16);
+  uint32_t d[8];
+  alice_digest(h, a, p, d);
   const uint32_t* e = a.e + (size_t)p * a.e_len;
   bool eq = true;
   for (uint32_t k = 0; k < a.e_len; ++k) eq = eq && (e[k] == (k < 8 ? d[k] : 0u));
@@ -234,16 +242,25 @@ __global__ void alice_hash_kernel(const AliceHashArgs a) {
   a.verdict[p] = (a.verdict[p] && eq) ? 1 : 0;
 }
 
-// Bob's e' = H(N, N+1, a_enc, mta, z, z', t, v, w [, X.x, X.y, u.x, u.y]) == e
-// (range_proofs.rs:413-441; BobProofExt adds the four coordinates, :428-435).  The
-// inputs are hashed as given, z', v, w as computed.  An e wider than 256 bits
-// never matches.  One thread per proof, as alice_hash_kernel.
-__global__ void bob_hash_kernel(const BobHashArgs a) {
+// the prover's challenge: the same transcript, e written as 8 little-endian limbs
+__global__ void alice_challenge_kernel(const AliceHashArgs a, uint32_t* e_out) {
   const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= a.count) return;
   __shared__ uint32_t sha_w[64 * 16];  // launch blocks are 64 threads
   Sha256 h;
   h.init(sha_w + threadIdx.x * 16);
+  uint32_t d[8];
+  alice_digest(h, a, p, d);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) e_out[(size_t)p * 8 + k] = d[k];
+}
+
+// Bob's e' = H(N, N+1, a_enc, mta, z, z', t, v, w [, X.x, X.y, u.x, u.y]) == e
+// (range_proofs.rs:413-441; BobProofExt adds the four coordinates, :428-435).  The
+// inputs are hashed as given, z', v, w as computed.  An e wider than 256 bits
+// never matches.  One thread per proof, as alice_hash_kernel.  bob_digest: the
+// transcript's digest as 8 little-endian limbs (h initialised by the caller).
+__device__ __forceinline__ void bob_digest(Sha256& h, const BobHashArgs& a, uint32_t p, uint32_t* d) {
   const uint32_t* N = P32(a.n_ptr[p]);
   h.bigint(N, a.n_len);
   {
@@ -270,8 +287,17 @@ __global__ void bob_hash_kernel(const BobHashArgs a) {
     h.bigint(a.u + (size_t)p * 16, 8);
     h.bigint(a.u + (size_t)p * 16 + 8, 8);
   }
-  uint32_t d[8];
   h.finish_le(d);
+}
+
+__global__ void bob_hash_kernel(const BobHashArgs a) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= a.count) return;
+  __shared__ uint32_t sha_w[64 * 16];  // launch blocks are 64 threads
+  Sha256 h;
+  h.init(sha_w + threadIdx.x * 16);
+  uint32_t d[8];
+  bob_digest(h, a, p, d);
   const uint32_t* e = a.e + (size_t)p * a.e_len;
   bool eq = true;
   for (uint32_t k = 0; k < a.e_len; ++k) eq = eq && (e[k] == (k < 8 ? d[k] : 0u));
@@ -279,11 +305,37 @@ __global__ void bob_hash_kernel(const BobHashArgs a) {
   a.verdict[p] = (a.verdict[p] && eq) ? 1 : 0;
 }
 
+// the prover's challenge (range_proofs.rs:297-326): the same transcript, e written
+// as 8 little-endian limbs
+__global__ void bob_challenge_kernel(const BobHashArgs a, uint32_t* e_out) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= a.count) return;
+  __shared__ uint32_t sha_w[64 * 16];  // launch blocks are 64 threads
+  Sha256 h;
+  h.init(sha_w + threadIdx.x * 16);
+  uint32_t d[8];
+  bob_digest(h, a, p, d);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) e_out[(size_t)p * 8 + k] = d[k];
+}
+
 // ------------------------------------------------------------- launchers -------
 hipError_t launch_bob_hash(const BobHashArgs& a, hipStream_t st) {
   if (!a.count) return hipSuccess;
   if (a.n_len > 127u || (a.X == nullptr) != (a.u == nullptr)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(bob_hash_kernel, dim3(blocks_for(a.count, 64)), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_bob_challenge(const BobHashArgs& a, uint32_t* e_out, hipStream_t st) {
+  if (!a.count) return hipSuccess;
+  if (a.n_len > 127u || !e_out || (a.X == nullptr) != (a.u == nullptr)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(bob_challenge_kernel, dim3(blocks_for(a.count, 64)), dim3(64), 0, st, a, e_out);
+  return hipGetLastError();
+}
+hipError_t launch_alice_challenge(const AliceHashArgs& a, uint32_t* e_out, hipStream_t st) {
+  if (!a.count) return hipSuccess;
+  if (a.n_len > 127u || !e_out) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(alice_challenge_kernel, dim3(blocks_for(a.count, 64)), dim3(64), 0, st, a, e_out);
   return hipGetLastError();
 }
 hipError_t launch_binom(const BinomArgs& a, hipStream_t st) {

@@ -72,6 +72,44 @@ class AliceBatchC(ctypes.Structure):
                [(f, u32p) for f in ("N", "Ntilde", "h1", "h2", "key_idx", "cipher", "z", "s", "e", "s1", "s2")]
 
 
+class BobProveC(ctypes.Structure):
+    """struct fsdkr_bob_prove_batch (include/fsdkr/fsdkr.h)."""
+    SECRET = ("b", "beta_prim", "r", "alpha", "beta", "gamma", "gamma_mod_n", "ro", "ro_prim", "sigma", "tau")
+    _fields_ = [(f, ctypes.c_uint32) for f in ("count", "n_keys", "nl")] + \
+               [(f, u32p) for f in ("N", "Ntilde", "h1", "h2", "key_idx", "a_enc", "mta") + SECRET]
+
+
+class BobProofsC(ctypes.Structure):
+    """struct fsdkr_bob_proofs."""
+    _fields_ = [(f, u32p) for f in ("z", "t", "s", "e", "s1", "s2", "t1", "t2")]
+
+
+class AliceProveC(ctypes.Structure):
+    """struct fsdkr_alice_prove_batch."""
+    SECRET = ("a", "r", "alpha", "beta", "gamma", "ro")
+    _fields_ = [(f, ctypes.c_uint32) for f in ("count", "n_keys", "nl")] + \
+               [(f, u32p) for f in ("N", "Ntilde", "h1", "h2", "key_idx", "cipher") + SECRET]
+
+
+class AliceProofsC(ctypes.Structure):
+    """struct fsdkr_alice_proofs."""
+    _fields_ = [(f, u32p) for f in ("z", "s", "e", "s1", "s2")]
+
+
+def bob_prove_widths(nl):
+    """Limbs of every row of fsdkr_bob_prove in the width class nl: the inputs, then
+    the outputs (limbs(e x + y) = max(xl + 8, yl) + 1)."""
+    return ({"b": 8, "beta_prim": nl, "r": nl, "alpha": 24, "beta": nl, "gamma": nl + 16, "gamma_mod_n": nl,
+             "ro": nl + 8, "ro_prim": nl + 24, "sigma": nl + 8, "tau": nl + 24},
+            {"z": nl, "t": nl, "s": nl, "e": 8, "s1": 25, "s2": nl + 25, "t1": nl + 17, "t2": nl + 25})
+
+
+def alice_prove_widths(nl):
+    """Limbs of every row of fsdkr_alice_prove in the width class nl."""
+    return ({"a": 24, "r": nl, "alpha": 24, "beta": nl, "gamma": nl + 24, "ro": nl + 8},
+            {"z": nl, "s": nl, "e": 8, "s1": 33, "s2": nl + 25})
+
+
 class RecoverJobC(ctypes.Structure):
     _fields_ = [("nl", ctypes.c_uint32), ("t_vss", ctypes.c_uint32), ("t_key", ctypes.c_uint32),
                 ("n_new", ctypes.c_uint32), ("old_index", u32p), ("cts", u32p), ("p", u32p), ("q", u32p),
@@ -247,6 +285,12 @@ def lib():
     L.fsdkr_ring_pedersen_verify.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                              u32p, u32p, u32p, u32p, u32p, u8p]
     L.fsdkr_ring_pedersen_verify.restype = ctypes.c_int
+    L.fsdkr_bob_prove.argtypes = [vp, ctypes.POINTER(BobProveC), ctypes.POINTER(BobProofsC)]
+    L.fsdkr_bob_prove.restype = ctypes.c_int
+    L.fsdkr_alice_prove.argtypes = [vp, ctypes.POINTER(AliceProveC), ctypes.POINTER(AliceProofsC)]
+    L.fsdkr_alice_prove.restype = ctypes.c_int
+    L.fsdkr_resp_ct.argtypes = [vp, ctypes.c_uint32, u32p, u32p, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p]
+    L.fsdkr_resp_ct.restype = ctypes.c_int
     _lib = L
     return L
 
@@ -690,6 +734,82 @@ class Context:
         finally:
             X.fill(0)
             Y.fill(0)
+        return limbs_to_ints(O)
+
+    def _prove(self, fn, batch_cls, out_cls, widths, keys, key_idx, nl, public, secret):
+        """One whole-prover call: `public` / `secret` map field names to lists of ints,
+        packed with ints_to_limbs to the fixed widths; the secret staging arrays are
+        zeroed whatever happens.  Returns {field: [int]}."""
+        win, wout = widths
+        count = len(key_idx)
+        for name, vals in list(public.items()) + list(secret.items()):
+            if len(vals) != count:
+                raise ValueError(f"{fn.__name__}: {name} differs in length")
+        if count == 0:
+            return {f: [] for f in wout}
+        b, o = batch_cls(), out_cls()
+        b.count, b.n_keys, b.nl = count, len(keys), nl
+        keep, staged = [], []
+        try:
+            for col, name in enumerate(("N", "Ntilde", "h1", "h2")):
+                keep.append(ints_to_limbs([k[col] for k in keys], nl))
+                setattr(b, name, _ptr(keep[-1]))
+            keep.append(np.ascontiguousarray(np.asarray(key_idx, dtype=np.uint32)))
+            b.key_idx = _ptr(keep[-1])
+            for name, vals in public.items():
+                keep.append(ints_to_limbs(list(vals), 2 * nl))
+                setattr(b, name, _ptr(keep[-1]))
+            for name in batch_cls.SECRET:
+                staged.append(ints_to_limbs(list(secret[name]), win[name]))
+                setattr(b, name, _ptr(staged[-1]))
+            outs = {f: np.zeros((count, w), dtype=np.uint32) for f, w in wout.items()}
+            for f, a in outs.items():
+                setattr(o, f, _ptr(a))
+            self.check(fn(self._h, ctypes.byref(b), ctypes.byref(o)))
+        finally:
+            for S in staged:
+                S.fill(0)
+        return {f: limbs_to_ints(a) for f, a in outs.items()}
+
+    def bob_prove(self, keys, key_idx, nl, a_encs, mtas, **secret):
+        """BobProof::generate of every proof in ONE device call (fsdkr_bob_prove).  keys:
+        [(N, N~, h1, h2)] with h1, h2 < N~; a_encs reduced mod N^2; mtas hashed as given.
+        SECRET keyword lists, each a draw or a witness per proof (BobProveC.SECRET): b,
+        beta_prim, r, alpha, beta, gamma, gamma_mod_n (= gamma mod N), ro, ro_prim,
+        sigma, tau.  ValueError for a negative value or one wider than its row
+        (bob_prove_widths).  Returns {z, t, s, e, s1, s2, t1, t2: [int]}."""
+        if set(secret) != set(BobProveC.SECRET):
+            raise ValueError(f"bob_prove: needs exactly {BobProveC.SECRET}")
+        return self._prove(self._lib.fsdkr_bob_prove, BobProveC, BobProofsC, bob_prove_widths(nl), keys, key_idx, nl,
+                           {"a_enc": a_encs, "mta": mtas}, secret)
+
+    def alice_prove(self, keys, key_idx, nl, ciphers, **secret):
+        """AliceProof::generate of every proof in ONE device call (fsdkr_alice_prove).
+        keys as in bob_prove; ciphers hashed as given.  SECRET keyword lists
+        (AliceProveC.SECRET): a, r, alpha, beta, gamma, ro.  Returns {z, s, e, s1, s2: [int]}."""
+        if set(secret) != set(AliceProveC.SECRET):
+            raise ValueError(f"alice_prove: needs exactly {AliceProveC.SECRET}")
+        return self._prove(self._lib.fsdkr_alice_prove, AliceProveC, AliceProofsC, alice_prove_widths(nl), keys, key_idx,
+                           nl, {"cipher": ciphers}, secret)
+
+    def resp_ct(self, es, xs, ys, xl, yl):
+        """[e x + y] as integers through resp_ct_kernel (fsdkr_resp_ct): es public
+        (< 2^256), xs / ys SECRET rows of xl / yl limbs (1 .. 128)."""
+        count = len(es)
+        if not (len(xs) == len(ys) == count):
+            raise ValueError("resp_ct: argument lists differ in length")
+        if count == 0:
+            return []
+        X = Y = None
+        try:
+            E = ints_to_limbs(list(es), 8)
+            X, Y = ints_to_limbs(list(xs), xl), ints_to_limbs(list(ys), yl)
+            O = np.zeros((count, max(xl + 8, yl) + 1), dtype=np.uint32)
+            self.check(self._lib.fsdkr_resp_ct(self._h, count, _ptr(E), _ptr(X), xl, _ptr(Y), yl, _ptr(O)))
+        finally:
+            for S in (X, Y):
+                if S is not None:
+                    S.fill(0)
         return limbs_to_ints(O)
 
     def pdl_u1_check(self, s1s, es, Qs, u1s):

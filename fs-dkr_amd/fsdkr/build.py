@@ -23,7 +23,7 @@ SOURCES = ["modexp.hip", "fixedbase.hip", "comb.hip", "inverse.hip", "vhash.hip"
            "prime.hip", "capi.cpp", "keygen.cpp", "collect.cpp", "collect_prestart.cpp", "collect_prepare.cpp",
            "collect_launch.cpp", "recover.cpp", "standalone.cpp", "mta.cpp", "fixedbase_host.cpp", "ec_ct.hip",
            "ec_ct_host.cpp", "mta_ct.hip", "comb_ct.hip", "comb_ct_host.cpp",
-           "mta_alice.cpp"]
+           "mta_alice.cpp", "resp_ct.hip", "mta_prove.cpp"]
 CFLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-I", INCLUDE, "-I", CSRC,
           "-Wno-unused-result"]
 

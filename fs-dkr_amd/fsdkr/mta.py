@@ -27,7 +27,13 @@ respond      Bob's side of one exchange ("Bob follows MtA", :688-704): the
              response mta_out = a_enc^b * Enc(beta'; r) on the device
              (fsdkr_mta_respond: one constant-time chain per response in both
              width classes), then its proofs (generate_bob).
-finish       Alice's last step: alpha = Dec(mta_out) mod q."""
+finish       Alice's last step: alpha = Dec(mta_out) mod q.
+
+one_call=True (generate_bob, generate_alice, and through them respond, initiate)
+             the whole prover as ONE device call (Context.bob_prove / alice_prove,
+             fsdkr_bob_prove / fsdkr_alice_prove): the same draws, then the
+             commitments, the challenge hash, r^e beta mod N and the integer
+             responses all on the device; bit for bit the default path's proofs."""
 import math
 
 import numpy as np
@@ -262,7 +268,19 @@ def commit_yl(nl):
     return ALICE_XL + nl
 
 
-def generate_alice(items, rng, ctx=None):
+def _prove_keys(eks, sts):
+    """The key table of a whole-prover call: ([(N, N~, h1 mod N~, h2 mod N~)], key_idx)."""
+    keys, row, idx = [], {}, []
+    for ek, st in zip(eks, sts):
+        k = (ek.n, st.N, st.g % st.N, st.ni % st.N)
+        if k not in row:
+            row[k] = len(keys)
+            keys.append(k)
+        idx.append(row[k])
+    return keys, idx
+
+
+def generate_alice(items, rng, ctx=None, one_call=False):
     """AliceProof::generate (range_proofs.rs:168-202) for every item (a, cipher, ek,
     statement, r): Alice's secret a in [0, 2^768), her ciphertext cipher = Enc(a; r)
     under her key ek, the verifier's (N~, h1, h2) and the randomness r.
@@ -273,7 +291,12 @@ def generate_alice(items, rng, ctx=None):
     instances per proof, x rows of 24 limbs, y rows of commit_yl limbs: public bounds,
     so the kernel's geometry tells nothing about the values); u = Enc(alpha; beta) runs
     through Context.paillier_encrypt and s = r^e beta mod N through modexp_batch (e is
-    public).  Returns types.AliceProofs."""
+    public).  Returns types.AliceProofs.
+
+    one_call=True: the same draws in the same order and bit for bit the same proofs
+    from exactly ONE Context.alice_prove call (fsdkr_alice_prove: the comb, u, the
+    challenge hash, r^e beta and the responses e a + alpha, e ro + gamma on the device;
+    nothing secret is combined in host integers)."""
     ctx = _ctx(ctx)
     items = list(items)
     n = len(items)
@@ -291,6 +314,12 @@ def generate_alice(items, rng, ctx=None):
         gamma = rng.sample_below(Q3 * st.N)
         ro = rng.sample_below(Q * st.N)
         rnd.append((alpha, beta, gamma, ro))
+    if one_call:
+        keys, idx = _prove_keys(eks, sts)
+        o = ctx.alice_prove(keys, idx, nl, [it[1] for it in items], a=[it[0] for it in items],
+                            r=[it[4] % ek.n for it, ek in zip(items, eks)], alpha=[x[0] for x in rnd],
+                            beta=[x[1] for x in rnd], gamma=[x[2] for x in rnd], ro=[x[3] for x in rnd])
+        return [AliceProof(o["z"][k], o["e"][k], o["s"][k], o["s1"][k], o["s2"][k]) for k in range(n)]
     keys, row = [], {}
     for st in sts:
         k = (st.N, st.g % st.N, st.ni % st.N)
@@ -321,7 +350,7 @@ def generate_alice(items, rng, ctx=None):
     return out
 
 
-def initiate(as_, eks, statements, rng, ctx=None):
+def initiate(as_, eks, statements, rng, ctx=None, one_call=False):
     """Alice starts MtA (range_proofs.rs:650-670) for every exchange k: her secret
     as_[k] (0 <= a < q), her own Paillier key eks[k] and Bob's (N~, h1, h2)
     statements[k].
@@ -329,7 +358,7 @@ def initiate(as_, eks, statements, rng, ctx=None):
     First, for every exchange in order, r_k = from_modulo(N_k) through `rng` (:656);
     then ONE Context.paillier_encrypt call makes every c_A = Enc(a; r), at the width
     class of the call's keys (width_class); then ONE generate_alice call over the same
-    rng proves them.  Returns (a_encs, rs, proofs)."""
+    rng proves them.  Returns (a_encs, rs, proofs).  one_call is generate_alice's."""
     ctx = _ctx(ctx)
     as_, eks, statements = list(as_), list(eks), list(statements)
     n = len(as_)
@@ -348,7 +377,7 @@ def initiate(as_, eks, statements, rng, ctx=None):
             n_row[ek.n] = len(ns)
             ns.append(ek.n)
     a_encs = ctx.paillier_encrypt(as_, rs, ns, [n_row[ek.n] for ek in eks], nl)
-    proofs = generate_alice(list(zip(as_, a_encs, eks, statements, rs)), rng, ctx=ctx)
+    proofs = generate_alice(list(zip(as_, a_encs, eks, statements, rs)), rng, ctx=ctx, one_call=one_call)
     return a_encs, rs, proofs
 
 
@@ -394,7 +423,7 @@ def _bob_round1_fused(ctx, items, rnd, nl):
     return [tuple(cm[4 * k:4 * k + 4]) for k in range(len(items))], vs
 
 
-def generate_bob(items, rng, ctx=None, check=False, fused=False):
+def generate_bob(items, rng, ctx=None, check=False, fused=False, one_call=False):
     """BobProof::generate (range_proofs.rs:448-515) / BobProofExt::generate
     (:564-589) for every item (a_enc, mta_out, b, beta_prim, ek, statement, r):
     Alice's ciphertext, the MtA output, Bob's secret scalar b in [0, q), the
@@ -411,13 +440,26 @@ def generate_bob(items, rng, ctx=None, check=False, fused=False):
     constant-time two-base comb, 4 n instances at public widths) and every v from ONE
     Context.bob_commit_v call (fsdkr_bob_commit_v: one constant-time chain per v in
     both width classes); no regular-access modexp is issued.  It needs 0 <= b <
-    2^256 and 0 <= beta' < N (ValueError before any device call otherwise)."""
+    2^256 and 0 <= beta' < N (ValueError before any device call otherwise).
+
+    one_call=True: the same draws in the same order and bit for bit the same proofs
+    from exactly ONE Context.bob_prove call (fsdkr_bob_prove: the comb and the v chain
+    of fused=True, then the challenge hash, r^e beta mod N and the four responses
+    e x + y on the device; nothing secret is combined in host integers).  It needs what
+    fused=True needs and 0 <= a_enc < N^2, and has no BobProofExt yet: check=True is a
+    ValueError, as the others before any device call."""
     ctx = _ctx(ctx)
     items = list(items)
     n = len(items)
     if n == 0:
         return []
-    if fused:
+    if one_call:
+        if check:
+            raise ValueError("generate_bob: one_call has no BobProofExt (check=True)")
+        for a_enc, mta, b, beta_prim, ek, st, r in items:
+            if a_enc < 0 or a_enc >= ek.nn:
+                raise ValueError("generate_bob: one_call needs 0 <= a_enc < N^2")
+    if fused or one_call:
         for a_enc, mta, b, beta_prim, ek, st, r in items:
             if b < 0 or b >> 256:
                 raise ValueError("generate_bob: b must satisfy 0 <= b < 2^256")
@@ -434,6 +476,16 @@ def generate_bob(items, rng, ctx=None, check=False, fused=False):
         sigma = rng.sample_below(Q * st.N)
         tau = rng.sample_below(Q3 * st.N)
         rnd.append((alpha, beta, gamma, ro, ro_prim, sigma, tau))
+    if one_call:
+        eks = [it[4] for it in items]
+        keys, idx = _prove_keys(eks, [it[5] for it in items])
+        o = ctx.bob_prove(keys, idx, nl, [it[0] for it in items], [it[1] for it in items], b=[it[2] for it in items],
+                          beta_prim=[it[3] for it in items], r=[it[6] % it[4].n for it in items],
+                          alpha=[x[0] for x in rnd], beta=[x[1] for x in rnd], gamma=[x[2] for x in rnd],
+                          gamma_mod_n=[x[2] % ek.n for x, ek in zip(rnd, eks)], ro=[x[3] for x in rnd],
+                          ro_prim=[x[4] for x in rnd], sigma=[x[5] for x in rnd], tau=[x[6] for x in rnd])
+        return [BobProof(o["t"][k], o["z"][k], o["e"][k], o["s"][k], o["s1"][k], o["s2"][k], o["t1"][k], o["t2"][k])
+                for k in range(n)]
     # round 1: h1^(b, alpha, beta', gamma), h2^(ro, ro', sigma, tau) mod N~; a_enc^alpha, beta^N mod N^2
     if fused:
         commits, vs = _bob_round1_fused(ctx, items, rnd, nl)
@@ -499,7 +551,7 @@ def _bob_round1_composed(ctx, items, rnd, nl):
     return commits, vs
 
 
-def respond(a_encs, bs, eks, statements, rng, ctx=None, check=False, fused_proofs=False):
+def respond(a_encs, bs, eks, statements, rng, ctx=None, check=False, fused_proofs=False, one_call=False):
     """Bob follows MtA (range_proofs.rs:688-715) for every exchange k: Alice's
     ciphertext a_encs[k] under her key eks[k], Bob's secret scalar bs[k] (0 <= b <
     2^256) and Alice's (N~, h1, h2) statements[k].
@@ -512,7 +564,8 @@ def respond(a_encs, bs, eks, statements, rng, ctx=None, check=False, fused_proof
 
     Returns (mta_outs, betas, proofs): the responses, Bob's additive shares
     beta = -beta' mod q, and BobProofs (check=True: BobProofExts, whose verifier
-    takes X = G*b).  fused_proofs is generate_bob's `fused`."""
+    takes X = G*b).  fused_proofs is generate_bob's `fused`, one_call its `one_call`
+    (the response itself stays its own Context.mta_respond call)."""
     ctx = _ctx(ctx)
     a_encs, bs, eks, statements = list(a_encs), list(bs), list(eks), list(statements)
     n = len(a_encs)
@@ -537,7 +590,7 @@ def respond(a_encs, bs, eks, statements, rng, ctx=None, check=False, fused_proof
     mta_outs = ctx.mta_respond(a_red, bs, [d[0] for d in draws], [d[1] for d in draws], ns,
                                [n_row[ek.n] for ek in eks], nl)
     items = [(a, m, b, d[0], ek, st, d[1]) for a, m, b, d, ek, st in zip(a_encs, mta_outs, bs, draws, eks, statements)]
-    proofs = generate_bob(items, rng, ctx=ctx, check=check, fused=fused_proofs)
+    proofs = generate_bob(items, rng, ctx=ctx, check=check, fused=fused_proofs, one_call=one_call)
     return mta_outs, [(-d[0]) % Q for d in draws], proofs
 
 

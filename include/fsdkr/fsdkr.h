@@ -519,6 +519,120 @@ int fsdkr_pedersen_commit_ct(fsdkr_ctx* ctx, uint32_t nl, uint32_t count,
                              const uint32_t* Ntilde, const uint32_t* h1, const uint32_t* h2, /* [n_keys][nl] */
                              uint32_t n_keys, uint32_t* out);  /* [count][nl] */
 
+/* ---- The MtA provers in one call -------------------------------------------------
+ * fsdkr_bob_prove is BobProof::generate (range_proofs.rs:448-515) and
+ * fsdkr_alice_prove is AliceProof::generate (:168-202) for `count` proofs, laid out
+ * like fsdkr_bob_batch: a table of n_keys keys (N the Paillier modulus the proof is
+ * under, Ntilde, h1, h2 the verifier's), key_idx[p] the row of proof p, one width
+ * class nl (64 or 96) per call with narrower keys zero-extended.  Every draw is an
+ * input: the caller owns the randomness.  Rows are little-endian 32-bit limbs of the
+ * fixed widths below, zero-extended; the entries are defined on rows, not on the
+ * reference's bounds.
+ *
+ * Bob: z = h1^b h2^ro, z' = h1^alpha h2^ro_prim, t = h1^beta_prim h2^sigma and
+ * w = h1^gamma h2^tau mod Ntilde come from ONE launch of the constant-time comb of
+ * fsdkr_pedersen_commit_ct (4 count instances, x rows of nl + 16 limbs, y rows of
+ * nl + 24); v = a_enc^alpha (1 + gamma_mod_n N) beta^N mod N^2 from the chain of
+ * fsdkr_bob_commit_v.  Then, without leaving the device: e = H(N, N + 1, a_enc, mta,
+ * z, z', t, v, w) (SHA-256 over the minimal big-endian bytes, a_enc and mta hashed as
+ * given), r^e mod N by the public-exponent kernel with e read from the hash kernel's
+ * output, s = r^e beta mod N by one exact modular product, and the integer responses
+ * s1 = e b + alpha, s2 = e ro + ro_prim, t1 = e beta_prim + gamma, t2 = e sigma + tau
+ * (resp_ct_kernel).
+ * Alice: z = h1^a h2^ro and w = h1^alpha h2^gamma from ONE comb launch (2 count
+ * instances, x rows of 24 limbs, y rows of nl + 24); u = (1 + alpha N) beta^N mod N^2
+ * from the same constant-time chain as Bob's v (a_enc = 1, a zero exponent row), so
+ * alpha enters through the constant-time binomial; e = H(N, N + 1, cipher, z, u, w);
+ * s = r^e beta mod N, s1 = e a + alpha, s2 = e ro + gamma.
+ *
+ * The rows marked SECRET have the guarantees of fsdkr_mta_respond: no address, branch
+ * or trip count on the device depends on them; before the call returns every device
+ * buffer that held one of them, a digit schedule made from one, r^e, or the window
+ * table of the r^e chain is zeroed, and the host staging rows are wiped.  The
+ * commitments and the challenge are public and pass through host memory between the
+ * stages, as the component entries return them.  beta, r and gamma_mod_n must be
+ * below N and gamma_mod_n must be gamma mod N: they are secret and not checked.
+ * For fsdkr_alice_prove alpha must be below N as well (it enters u as 1 + alpha N
+ * without a reduction): every N of 768 bits or more satisfies this for any alpha row,
+ * and Alice's keys below 768 bits are outside the entry's domain.
+ * a_enc must be reduced mod N^2 (FSDKR_E_ARG otherwise); mta and cipher are only
+ * hashed.  nl other than 64 or 96: FSDKR_E_UNSUPPORTED.  Even N or Ntilde, N or
+ * Ntilde <= 1, h1 or h2 >= Ntilde, key_idx out of range, a NULL pointer:
+ * FSDKR_E_ARG.  count == 0: OK.  A context forced to a lane count that the comb or the
+ * chain refuses (fsdkr_ctx_set_modexp_group) gets that entry's error. */
+typedef struct fsdkr_bob_prove_batch {
+  uint32_t count, n_keys, nl;
+  const uint32_t* N;            /* [n_keys][nl]  alice_ek.n                 */
+  const uint32_t* Ntilde;       /* [n_keys][nl]  dlog_statement.N           */
+  const uint32_t* h1;           /* [n_keys][nl]  dlog_statement.g, < Ntilde  */
+  const uint32_t* h2;           /* [n_keys][nl]  dlog_statement.ni, < Ntilde */
+  const uint32_t* key_idx;      /* [count]                                  */
+  const uint32_t* a_enc;        /* [count][2nl]  reduced mod N^2            */
+  const uint32_t* mta;          /* [count][2nl]  hashed as given            */
+  const uint32_t* b;            /* [count][8]       SECRET */
+  const uint32_t* beta_prim;    /* [count][nl]      SECRET */
+  const uint32_t* r;            /* [count][nl]      SECRET, < N */
+  const uint32_t* alpha;        /* [count][24]      SECRET */
+  const uint32_t* beta;         /* [count][nl]      SECRET, < N */
+  const uint32_t* gamma;        /* [count][nl + 16] SECRET */
+  const uint32_t* gamma_mod_n;  /* [count][nl]      SECRET, gamma mod N */
+  const uint32_t* ro;           /* [count][nl + 8]  SECRET */
+  const uint32_t* ro_prim;      /* [count][nl + 24] SECRET */
+  const uint32_t* sigma;        /* [count][nl + 8]  SECRET */
+  const uint32_t* tau;          /* [count][nl + 24] SECRET */
+} fsdkr_bob_prove_batch;
+
+typedef struct fsdkr_bob_proofs {   /* limbs(e x + y) = max(xl + 8, yl) + 1 */
+  uint32_t* z;    /* [count][nl]      */
+  uint32_t* t;    /* [count][nl]      */
+  uint32_t* s;    /* [count][nl]      */
+  uint32_t* e;    /* [count][8]       */
+  uint32_t* s1;   /* [count][25]      */
+  uint32_t* s2;   /* [count][nl + 25] */
+  uint32_t* t1;   /* [count][nl + 17] */
+  uint32_t* t2;   /* [count][nl + 25] */
+} fsdkr_bob_proofs;
+
+int fsdkr_bob_prove(fsdkr_ctx* ctx, const fsdkr_bob_prove_batch* batch, fsdkr_bob_proofs* out);
+
+typedef struct fsdkr_alice_prove_batch {
+  uint32_t count, n_keys, nl;
+  const uint32_t* N;            /* [n_keys][nl]  alice_ek.n                 */
+  const uint32_t* Ntilde;       /* [n_keys][nl]  dlog_statement.N           */
+  const uint32_t* h1;           /* [n_keys][nl]  < Ntilde                    */
+  const uint32_t* h2;           /* [n_keys][nl]  < Ntilde                    */
+  const uint32_t* key_idx;      /* [count]                                  */
+  const uint32_t* cipher;       /* [count][2nl]  hashed as given            */
+  const uint32_t* a;            /* [count][24]      SECRET */
+  const uint32_t* r;            /* [count][nl]      SECRET, < N */
+  const uint32_t* alpha;        /* [count][24]      SECRET */
+  const uint32_t* beta;         /* [count][nl]      SECRET, < N */
+  const uint32_t* gamma;        /* [count][nl + 24] SECRET */
+  const uint32_t* ro;           /* [count][nl + 8]  SECRET */
+} fsdkr_alice_prove_batch;
+
+typedef struct fsdkr_alice_proofs {
+  uint32_t* z;    /* [count][nl]      */
+  uint32_t* s;    /* [count][nl]      */
+  uint32_t* e;    /* [count][8]       */
+  uint32_t* s1;   /* [count][33]      */
+  uint32_t* s2;   /* [count][nl + 25] */
+} fsdkr_alice_proofs;
+
+int fsdkr_alice_prove(fsdkr_ctx* ctx, const fsdkr_alice_prove_batch* batch, fsdkr_alice_proofs* out);
+
+/* Parity entry of the provers' response kernel (resp_ct_kernel), as
+ * fsdkr_modexp_joint3_batch is for the verifier's tail: out = e x + y over 32-bit
+ * limbs, no modulus, for `count` rows.  e is public (8 limbs per row); x and y are
+ * SECRET, with the guarantees above (trip counts from xl and yl alone, a branch-free
+ * carry chain, the device rows zeroed before the call returns).  1 <= xl, yl <= 128,
+ * else FSDKR_E_ARG; a NULL pointer: FSDKR_E_ARG; count == 0: OK. */
+int fsdkr_resp_ct(fsdkr_ctx* ctx, uint32_t count,
+                  const uint32_t* e,                /* [count][8] */
+                  const uint32_t* x, uint32_t xl,   /* [count][xl] SECRET */
+                  const uint32_t* y, uint32_t yl,   /* [count][yl] SECRET */
+                  uint32_t* out);                   /* [count][max(xl + 8, yl) + 1] */
+
 /* Which prestarted parts the last fsdkr_collect_prepare[_multi] reused (bit
  * mask): 1 GA chains, 2 fixed-base tables, 4 correct-key job, 8 ring-Pedersen
  * T^Z exponents (multi-session).  0 before any prepare.  Diagnostic (tests
