@@ -708,9 +708,7 @@ int fsdkr::mta_respond_impl(Ctx* c, const char* who, uint32_t nl, uint32_t count
                      cons, (const uint32_t*)tb.ptr, (const uint32_t*)sb.ptr, w, PU(o_a), PU(o_b), PU(o_binom), t2,
                      PU(o_out), (uint32_t)n};
       c->mark(nm.mark, true);
-      rc = c->hip_check(nl == 64 ? (el == 8 ? launch_mta_tail_ct(ta, st) : launch_bob_v_tail_ct(ta, st))
-                                 : (el == 8 ? launch_mta_tail_ct6144(ta, st) : launch_bob_v_tail_ct6144(ta, st)),
-                        nm.mark);
+      rc = c->hip_check(launch_mta_tail_ct(nl, el, ta, st), nm.mark);
       c->mark(nm.mark, false);
       if (rc) return rc;
     } else {

@@ -183,27 +183,30 @@ struct EcMsmCtArgs {        // out[o] = sum_j scalars[o][j] * points[o][j]
 };
 
 // Bob's MtA response (mta_ct.hip): the constant-time joint tail of the split chain
-// r^N a_enc^b (1 + beta' N) mod N^2 at 128 limbs, 8 lanes per chain.  Whole waves,
-// no bound check: every per-instance array has count_pad rows, in launch order.
+// r^N a_enc^b (1 + beta' N) mod N^2, 8 lanes per chain.  Whole waves, no bound
+// check: every per-instance array has count_pad rows, in launch order.
 constexpr uint32_t kMtaTailPad = 8;    // instances per wave
 constexpr uint32_t kMtaTailLo = 256;   // the head's lo_bit: b < 2^256 rides the tail
 // Bob's commitment v = a_enc^alpha (1 + gamma N) beta^N mod N^2: the same tail over
 // 768 squarings (bob_v_tail_ct_kernel), alpha < q^3 in b's place at 24 limbs per row
 constexpr uint32_t kBobVTailLo = 768, kBobVLimbs = 24;
 
+// Row widths by the launch's (nl, el): kd = 144 digits and kl = 128 limbs at nl = 64
+// (N^2 < 2^4096), kd = 216 and kl = 192 at nl = 96 (N^2 < 2^6144); el = 8 limbs of
+// secret exponent for the response, kBobVLimbs for v (alpha in b's place).
 struct MtaTailArgs {
-  const uint64_t* exp_ptr;  // [count_pad] N's limbs (at least 8; bob_v: 24), shared by the instances of every wave
+  const uint64_t* exp_ptr;  // [count_pad] N's limbs (at least el), shared by the instances of every wave
   const uint32_t* mod_idx;  // [count_pad] row of consts
   const uint32_t* out_idx;  // [count_pad] output row
-  const uint32_t* consts;   // mod_setup rows of the 144-digit class (N^2 and its scaled block)
-  const uint32_t* table;    // the head's odd-power table [count_pad][2^(window-1) + 1][144]
-  const uint32_t* state;    // the head's accumulator [count_pad][144]
+  const uint32_t* consts;   // mod_setup rows of the kd-digit class (N^2 and its scaled block)
+  const uint32_t* table;    // the head's odd-power table [count_pad][2^(window-1) + 1][kd]
+  const uint32_t* state;    // the head's accumulator [count_pad][kd]
   uint32_t window;          // the head's sliding-window width
-  const uint32_t* a_enc;    // [count_pad][128] reduced mod N^2 (public)
-  const uint32_t* b;        // [count_pad][8] SECRET (bob_v: alpha, [count_pad][24])
-  const uint32_t* binom;    // [count_pad][128] 1 + beta' N (binom_ct_kernel) SECRET
-  uint32_t* table2;         // [count_pad][16][144] scratch: a_enc^u
-  uint32_t* out;            // rows of 128 limbs
+  const uint32_t* a_enc;    // [count_pad][kl] reduced mod N^2 (public)
+  const uint32_t* b;        // [count_pad][el] SECRET
+  const uint32_t* binom;    // [count_pad][kl] 1 + beta' N (binom_ct_kernel) SECRET
+  uint32_t* table2;         // [count_pad][16][kd] scratch: a_enc^u
+  uint32_t* out;            // rows of kl limbs
   uint32_t count_pad;       // a multiple of kMtaTailPad
 };
 
@@ -231,11 +234,8 @@ hipError_t launch_resp_ct(const RespCtArgs& a, hipStream_t st);
 hipError_t launch_bob_challenge(const BobHashArgs& a, uint32_t* e_out, hipStream_t st);
 hipError_t launch_alice_challenge(const AliceHashArgs& a, uint32_t* e_out, hipStream_t st);
 
-hipError_t launch_mta_tail_ct(const MtaTailArgs& a, hipStream_t st);
-hipError_t launch_bob_v_tail_ct(const MtaTailArgs& a, hipStream_t st);
-// the same tails at 192 limbs (216-digit rows, 192-limb a_enc / binom / out)
-hipError_t launch_mta_tail_ct6144(const MtaTailArgs& a, hipStream_t st);
-hipError_t launch_bob_v_tail_ct6144(const MtaTailArgs& a, hipStream_t st);
+// nl = 64 or 96, el = 8 or kBobVLimbs: one of the four tail kernels
+hipError_t launch_mta_tail_ct(uint32_t nl, uint32_t el, const MtaTailArgs& a, hipStream_t st);
 hipError_t launch_binom_ct(uint32_t nl, const BinomCtArgs& a, hipStream_t st);   // nl = 64 or 96
 hipError_t launch_binom(const BinomArgs& a, hipStream_t st);
 hipError_t launch_ped_hash(const PedHashArgs& a, hipStream_t st);
