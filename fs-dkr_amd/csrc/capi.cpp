@@ -677,8 +677,12 @@ int fsdkr_ctx_set_flags(fsdkr_ctx* ctx, uint32_t flags) {
   return rc;
 }
 
-int fsdkr_mod_inverse(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const uint32_t* y, const uint32_t* m,
-                      uint32_t* out, uint32_t* unit) {
+// fsdkr_mod_inverse and its grouped parity entry.  force_batch: sort equal moduli
+// into groups and run inverse_batch_kernel at every width, whatever the flags say
+// and even when no two instances share a modulus (scratch rows of shape_digits
+// words, as mta.cpp sizes them); otherwise the routing collect() relies on.
+static int mod_inverse_impl(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const uint32_t* y, const uint32_t* m,
+                            uint32_t* out, uint32_t* unit, bool force_batch) {
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
   if (!c) return FSDKR_E_ARG;
   if (count == 0) return FSDKR_OK;
@@ -722,7 +726,9 @@ int fsdkr_mod_inverse(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const 
   // simultaneous inversion, inverse_batch_kernel) where the width has that shape
   std::vector<uint32_t> order(count), gstart;
   for (uint32_t i = 0; i < count; ++i) order[i] = i;
-  const size_t kd = batch_inv_on(c) ? inverse_batch_scratch_words(mod_limbs) : 0;
+  const size_t kd = force_batch       ? (size_t)shape_digits(mod_limbs)
+                    : batch_inv_on(c) ? inverse_batch_scratch_words(mod_limbs)
+                                      : 0;
   if (kd) {
     auto row = [&](uint32_t i) { return m + (size_t)i * mod_limbs; };
     std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y2) {
@@ -733,7 +739,7 @@ int fsdkr_mod_inverse(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const 
     gstart.push_back(count);
   }
   c->mark("inverse", true);
-  if (kd && gstart.size() - 1 < count) {
+  if (kd && (force_batch || gstart.size() - 1 < count)) {
     uint8_t* g = (uint8_t*)c->buf("inv_grp", 4 * ((size_t)count + gstart.size()) + 1024);
     uint32_t* scr = (uint32_t*)c->buf("inv_grp_scratch", (size_t)count * kd * 4);
     if (!g || !scr) {
@@ -761,6 +767,16 @@ int fsdkr_mod_inverse(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const 
   if ((rc = c->hip_check(hipMemcpyAsync(unit, d_u, 4 * (size_t)count, hipMemcpyDeviceToHost, c->stream), "D2H unit")))
     return rc;
   return c->sync();
+}
+
+int fsdkr_mod_inverse(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const uint32_t* y, const uint32_t* m,
+                      uint32_t* out, uint32_t* unit) {
+  return mod_inverse_impl(ctx, mod_limbs, count, y, m, out, unit, false);
+}
+
+int fsdkr_mod_inverse_grouped(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const uint32_t* y,
+                              const uint32_t* m, uint32_t* out, uint32_t* unit) {
+  return mod_inverse_impl(ctx, mod_limbs, count, y, m, out, unit, true);
 }
 
 int fsdkr_modexp_batch(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const uint32_t* base,

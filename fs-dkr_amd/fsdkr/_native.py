@@ -267,6 +267,8 @@ def lib():
     L.fsdkr_ctx_set_flags.restype = ctypes.c_int
     L.fsdkr_mod_inverse.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p, u32p]
     L.fsdkr_mod_inverse.restype = ctypes.c_int
+    L.fsdkr_mod_inverse_grouped.argtypes = L.fsdkr_mod_inverse.argtypes
+    L.fsdkr_mod_inverse_grouped.restype = ctypes.c_int
     L.fsdkr_miller_rabin.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p]
     L.fsdkr_miller_rabin.restype = ctypes.c_int
     L.fsdkr_ec_msm.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p]
@@ -497,8 +499,10 @@ class Context:
     def flags(self):
         return self._flags
 
-    def mod_inverse(self, ys, ms, mod_limbs):
-        """[(y^-1 mod m or None)] on the GPU (None where gcd(y, m) != 1)."""
+    def mod_inverse(self, ys, ms, mod_limbs, grouped=False):
+        """[(y^-1 mod m or None)] on the GPU (None where gcd(y, m) != 1).
+        grouped: fsdkr_mod_inverse_grouped, the simultaneous-inversion kernel at
+        every width and for every group size (parity tests)."""
         count = len(ys)
         if count == 0:
             return []
@@ -506,7 +510,8 @@ class Context:
         M = ints_to_limbs(ms, mod_limbs)
         O = np.zeros((count, mod_limbs), dtype=np.uint32)
         U = np.zeros(count, dtype=np.uint32)
-        self.check(self._lib.fsdkr_mod_inverse(self._h, mod_limbs, count, _ptr(Y), _ptr(M), _ptr(O), _ptr(U)))
+        fn = self._lib.fsdkr_mod_inverse_grouped if grouped else self._lib.fsdkr_mod_inverse
+        self.check(fn(self._h, mod_limbs, count, _ptr(Y), _ptr(M), _ptr(O), _ptr(U)))
         return [v if u else None for v, u in zip(limbs_to_ints(O), U.tolist())]
 
     def miller_rabin(self, cands, bases, mod_limbs):

@@ -120,6 +120,17 @@ int fsdkr_modexp_batch_ct(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, co
 int fsdkr_mod_inverse(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const uint32_t* y, const uint32_t* m,
                       uint32_t* out, uint32_t* unit);
 
+/* fsdkr_mod_inverse through the simultaneous-inversion kernel at every width
+ * (mod_limbs in {64, 96, 128, 192}): equal moduli are always sorted into groups
+ * and each group inverted by inverse_batch_kernel (one binary-GCD inverse of the
+ * group's prefix product; a group of one, or a group whose product is not a
+ * unit, inverts each element on its own), whatever FSDKR_CFG_INV_EACH says.
+ * These are the launch shapes of fsdkr_bob_verify / fsdkr_alice_verify, which
+ * fsdkr_mod_inverse does not reach at 96 and 192 limbs.  Same contract and
+ * results.  Parity tests of that path. */
+int fsdkr_mod_inverse_grouped(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const uint32_t* y,
+                              const uint32_t* m, uint32_t* out, uint32_t* unit);
+
 /* Device-resident variant for benchmarking/integration: all pointers are
  * device pointers already in HBM; runs on the context stream and returns
  * after the kernels complete.  `exp_bits` bounds the exponent bit length. */
