@@ -44,13 +44,7 @@ struct Coop {
   __device__ __forceinline__ int64_t top_s64(int64_t v) const {
     return (int64_t)mk64(bcast_top<G>((uint32_t)v), bcast_top<G>((uint32_t)((uint64_t)v >> 32)));
   }
-  __device__ __forceinline__ uint32_t group_or(uint32_t v) const {
-    if constexpr (G >= 2) v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);
-    if constexpr (G >= 4) v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);
-    if constexpr (G >= 8) v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, false);
-    if constexpr (G >= 16) v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xF, 0xF, false);
-    return v;
-  }
+  __device__ __forceinline__ uint32_t group_or(uint32_t v) const { return fsdkr::group_or<G>(v); }
 
   // Normalise signed column values t (|t_j| < 2^62) into limbs x in [0, 2^30).
   // Returns T (every lane): value = sum x_j 2^(30 j) + T 2^(30 NLT).

@@ -114,6 +114,17 @@ __device__ __forceinline__ int group_max(int v) {
   if constexpr (G >= 64) v = max(v, __shfl_xor(v, 32));
   return v;
 }
+// group-wide OR over the G lanes (the same steps)
+template <int G>
+__device__ __forceinline__ uint32_t group_or(uint32_t v) {
+  if constexpr (G >= 2) v |= FSDKR_DPP(v, 0xB1);    // [1,0,3,2]
+  if constexpr (G >= 4) v |= FSDKR_DPP(v, 0x4E);    // [2,3,0,1]
+  if constexpr (G >= 8) v |= FSDKR_DPP(v, 0x141);   // row_half_mirror
+  if constexpr (G >= 16) v |= FSDKR_DPP(v, 0x140);  // row_mirror
+  if constexpr (G >= 32) v |= (uint32_t)__shfl_xor((int)v, 16);
+  if constexpr (G >= 64) v |= (uint32_t)__shfl_xor((int)v, 32);
+  return v;
+}
 
 __device__ __forceinline__ uint64_t mk64(uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; }
 

@@ -2,6 +2,7 @@
 //   fsdkr_feldman_check          validate_collect's Feldman loop (refresh_message.rs:177-188)
 //   fsdkr_ring_pedersen_verify   RingPedersenProof::verify (ring_pedersen_proof.rs:126-157)
 //   fsdkr_pdl_u1_check           PDLwSlackProof::verify's u1 equation (zk_pdl_with_slack.rs:124-127,158)
+//   fsdkr_eq_check, fsdkr_prod3  parity entries of vmont.hip's eq_check_kernel and prod3_kernel
 // JoinMessage::collect (add_party_message.rs:136-175) needs exactly these two
 // checks and none of the pair proofs, so it calls them instead of the whole
 // fsdkr_verify_collect pipeline.  Both run on the context stream; the ring-
@@ -30,6 +31,32 @@ uint32_t bit_len(const uint32_t* x, uint32_t limbs) {
   for (int k = (int)limbs - 1; k >= 0; --k)
     if (x[k]) return 32u * (uint32_t)k + 32u - (uint32_t)__builtin_clz(x[k]);
   return 0;
+}
+
+// moduli of the parity entries: n_mod odd values >= 3 of k32 limbs, every mod_idx in range
+int check_parity_moduli(Ctx* c, const char* who, uint32_t k32, uint32_t count, const uint32_t* mods, uint32_t n_mod,
+                        const uint32_t* mod_idx) {
+  if (k32 != 64 && k32 != 96 && k32 != 128 && k32 != 192) {
+    c->fail("%s: unsupported modulus width %u limbs", who, k32);
+    return FSDKR_E_UNSUPPORTED;
+  }
+  if (!mods || !mod_idx || !n_mod) {
+    c->fail("%s: null pointer or empty modulus table", who);
+    return FSDKR_E_ARG;
+  }
+  for (uint32_t m = 0; m < n_mod; ++m) {
+    const uint32_t* N = mods + (size_t)m * k32;
+    if ((N[0] & 1u) == 0 || (N[0] == 1 && hbn::is_zero_raw(N + 1, k32 - 1))) {
+      c->fail("%s: modulus %u is even or 1", who, m);
+      return FSDKR_E_ARG;
+    }
+  }
+  for (uint32_t i = 0; i < count; ++i)
+    if (mod_idx[i] >= n_mod) {
+      c->fail("%s: mod_idx[%u] out of range", who, i);
+      return FSDKR_E_ARG;
+    }
+  return FSDKR_OK;
 }
 
 }  // namespace
@@ -278,6 +305,171 @@ int fsdkr_ring_pedersen_verify(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, uint
     verdict[m] = mode[m] == 2 ? 2 : ped_verdict(e, M, panic[m]);
   }
   return FSDKR_OK;
+}
+
+// ---- parity entries of vmont.hip's eq_check_kernel and prod3_kernel --------------
+// Both upload the rows as given, run setup_moduli and the one launcher, and
+// download the kernel's output: nothing is reduced or recomputed on the host, so
+// a test sees exactly what the collect() pipeline's launches compute.
+int fsdkr_eq_check(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const uint32_t* a, uint32_t a_len,
+                   const uint32_t* b, uint32_t b_len, const uint32_t* cc, uint32_t c_len, const uint32_t* dd,
+                   uint32_t d_len, const uint32_t* sel, const uint32_t* sel_bits, const uint32_t* flags,
+                   const uint32_t* mods, uint32_t n_mod, const uint32_t* mod_idx, uint8_t* out) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return FSDKR_E_ARG;
+  const char* who = "fsdkr_eq_check";
+  const uint32_t K = mod_limbs;
+  if (count == 0) return FSDKR_OK;
+  if (!a || !b || !cc || !dd || !out) {
+    c->fail("%s: null pointer", who);
+    return FSDKR_E_ARG;
+  }
+  int rc;
+  if ((rc = check_parity_moduli(c, who, K, count, mods, n_mod, mod_idx))) return rc;
+  if (!a_len || !b_len || !c_len || !d_len || a_len > K || b_len > K || d_len > K || c_len > 2 * K) {
+    c->fail("%s: rows of 1 to %u limbs (c: to %u)", who, K, 2 * K);
+    return FSDKR_E_ARG;
+  }
+  // the words of sel_bits the rows index
+  size_t sel_words = 0;
+  if (sel)
+    for (uint32_t i = 0; i < count; ++i)
+      if (sel[i] != 0xFFFFFFFFu) sel_words = std::max(sel_words, (size_t)(sel[i] >> 5) + 1);
+  if (sel_words && !sel_bits) {
+    c->fail("%s: sel without sel_bits", who);
+    return FSDKR_E_ARG;
+  }
+  // the kernel's precondition (one sub_if_ge per side): a factor of each pair is below N
+  const uint32_t one_limb = 1;
+  for (uint32_t i = 0; i < count; ++i) {
+    const uint32_t* N = mods + (size_t)mod_idx[i] * K;
+    const uint32_t *ra = a + (size_t)i * a_len, *rb = b + (size_t)i * b_len, *rw = cc + (size_t)i * c_len;
+    const uint32_t* rd = dd + (size_t)i * d_len;
+    uint32_t dl = d_len;
+    if (sel && sel[i] != 0xFFFFFFFFu && !((sel_bits[sel[i] >> 5] >> (sel[i] & 31)) & 1u)) {
+      rd = &one_limb;
+      dl = 1;
+    }
+    const bool f = flags && (flags[i] & 1u);
+    if (hbn::cmp_raw(ra, a_len, N, K) >= 0 && hbn::cmp_raw(rb, b_len, N, K) >= 0) {
+      c->fail("%s: row %u: neither a nor b is below its modulus", who, i);
+      return FSDKR_E_ARG;
+    }
+    if (hbn::cmp_raw(rw, c_len, N, K) >= 0 && hbn::cmp_raw(rd, dl, N, K) >= 0) {
+      c->fail("%s: row %u: neither c nor the selected d is below its modulus", who, i);
+      return FSDKR_E_ARG;
+    }
+    // limbs of c above the modulus width are only looked at by the c < N test
+    if (c_len > K && !f && !hbn::is_zero_raw(rw + K, c_len - K)) {
+      c->fail("%s: row %u: c wider than %u limbs without the c < N flag", who, i, K);
+      return FSDKR_E_ARG;
+    }
+  }
+  const size_t C = count;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = al256(off + (bytes ? bytes : 1)); return o; };
+  const size_t oA = take(C * a_len * 4), oB = take(C * b_len * 4), oC = take(C * c_len * 4), oD = take(C * d_len * 4);
+  const size_t oOne = take((size_t)K * 4), oBits = take(sel_words * 4), oOps = take(C * sizeof(EqOperand));
+  const size_t oIdx = take(C * 4), oMods = take((size_t)n_mod * K * 4), oOut = take(C * 4);
+  uint8_t* d = (uint8_t*)c->buf("eqp_io", off);
+  if (!d) {
+    c->fail("%s: device allocation failed", who);
+    return FSDKR_E_OOM;
+  }
+  auto DA = [&](size_t o) { return (uint64_t)(uintptr_t)(d + o); };
+  std::vector<uint32_t> one(K, 0u);
+  one[0] = 1;
+  std::vector<EqOperand> ops(C);
+  for (size_t i = 0; i < C; ++i) {
+    EqOperand& e = ops[i];
+    e.a = DA(oA + i * a_len * 4);
+    e.b = DA(oB + i * b_len * 4);
+    e.c = DA(oC + i * c_len * 4);
+    e.d = DA(oD + i * d_len * 4);
+    e.a_len = a_len;
+    e.b_len = b_len;
+    e.c_len = c_len;
+    e.d_len = d_len;
+    e.sel = sel ? sel[i] : 0xFFFFFFFFu;
+    e.flags = flags ? flags[i] : 0u;
+  }
+  hipStream_t st = c->stream;
+  auto up = [&](size_t o, const void* src, size_t bytes) {
+    return c->hip_check(hipMemcpyAsync(d + o, src, bytes, hipMemcpyHostToDevice, st), "H2D eq_check");
+  };
+  if ((rc = up(oA, a, C * a_len * 4)) || (rc = up(oB, b, C * b_len * 4)) || (rc = up(oC, cc, C * c_len * 4)) ||
+      (rc = up(oD, dd, C * d_len * 4)) || (rc = up(oOne, one.data(), (size_t)K * 4)) ||
+      (sel_words && (rc = up(oBits, sel_bits, sel_words * 4))) || (rc = up(oOps, ops.data(), C * sizeof(EqOperand))) ||
+      (rc = up(oIdx, mod_idx, C * 4)) || (rc = up(oMods, mods, (size_t)n_mod * K * 4)) ||
+      (rc = c->hip_check(hipMemsetAsync(d + oOut, 0, C * 4, st), "memset eq_check")))
+    return rc;
+  uint32_t* cons = nullptr;
+  if ((rc = setup_moduli(c, K, (const uint32_t*)(d + oMods), n_mod, &cons, "eqp"))) return rc;
+  EqCheckArgs ea{(const EqOperand*)(d + oOps), (const uint32_t*)(d + oIdx), cons, (const uint32_t*)(d + oBits),
+                 DA(oOne), (uint32_t*)(d + oOut), count};
+  c->mark("eq_check", true);
+  rc = c->hip_check(launch_eq_check(K, ea, st), "eq_check");
+  c->mark("eq_check", false);
+  if (rc) return rc;
+  std::vector<uint32_t> eq(C);
+  if ((rc = c->hip_check(hipMemcpyAsync(eq.data(), d + oOut, C * 4, hipMemcpyDeviceToHost, st), "D2H eq_check")))
+    return rc;
+  if ((rc = c->sync())) return rc;
+  for (size_t i = 0; i < C; ++i) out[i] = (uint8_t)eq[i];
+  return FSDKR_OK;
+}
+
+int fsdkr_prod3(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const uint32_t* a, uint32_t a_len,
+                const uint32_t* b, uint32_t b_len, const uint32_t* cc, uint32_t c_len, const uint32_t* mods,
+                uint32_t n_mod, const uint32_t* mod_idx, uint32_t* out) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return FSDKR_E_ARG;
+  const char* who = "fsdkr_prod3";
+  const uint32_t K = mod_limbs;
+  if (count == 0) return FSDKR_OK;
+  if (!a || !b || !cc || !out) {
+    c->fail("%s: null pointer", who);
+    return FSDKR_E_ARG;
+  }
+  int rc;
+  if ((rc = check_parity_moduli(c, who, K, count, mods, n_mod, mod_idx))) return rc;
+  if (!a_len || !b_len || !c_len || a_len > K || b_len > K || c_len > K) {
+    c->fail("%s: rows of 1 to %u limbs", who, K);
+    return FSDKR_E_ARG;
+  }
+  const size_t C = count;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = al256(off + bytes); return o; };
+  const size_t oA = take(C * a_len * 4), oB = take(C * b_len * 4), oC = take(C * c_len * 4);
+  const size_t oOps = take(C * sizeof(Prod3Operand)), oIdx = take(C * 4), oMods = take((size_t)n_mod * K * 4);
+  const size_t oOut = take(C * K * 4);
+  uint8_t* d = (uint8_t*)c->buf("p3p_io", off);
+  if (!d) {
+    c->fail("%s: device allocation failed", who);
+    return FSDKR_E_OOM;
+  }
+  auto DA = [&](size_t o) { return (uint64_t)(uintptr_t)(d + o); };
+  std::vector<Prod3Operand> ops(C);
+  for (size_t i = 0; i < C; ++i)
+    ops[i] = Prod3Operand{DA(oA + i * a_len * 4), DA(oB + i * b_len * 4), DA(oC + i * c_len * 4), a_len, b_len, c_len, 0};
+  hipStream_t st = c->stream;
+  auto up = [&](size_t o, const void* src, size_t bytes) {
+    return c->hip_check(hipMemcpyAsync(d + o, src, bytes, hipMemcpyHostToDevice, st), "H2D prod3");
+  };
+  if ((rc = up(oA, a, C * a_len * 4)) || (rc = up(oB, b, C * b_len * 4)) || (rc = up(oC, cc, C * c_len * 4)) ||
+      (rc = up(oOps, ops.data(), C * sizeof(Prod3Operand))) || (rc = up(oIdx, mod_idx, C * 4)) ||
+      (rc = up(oMods, mods, (size_t)n_mod * K * 4)) ||
+      (rc = c->hip_check(hipMemsetAsync(d + oOut, 0, C * K * 4, st), "memset prod3")))
+    return rc;
+  uint32_t* cons = nullptr;
+  if ((rc = setup_moduli(c, K, (const uint32_t*)(d + oMods), n_mod, &cons, "p3p"))) return rc;
+  Prod3Args pa{(const Prod3Operand*)(d + oOps), (const uint32_t*)(d + oIdx), cons, (uint32_t*)(d + oOut), count};
+  c->mark("prod3", true);
+  rc = c->hip_check(launch_prod3(K, pa, st), "prod3");
+  c->mark("prod3", false);
+  if (rc) return rc;
+  if ((rc = c->hip_check(hipMemcpyAsync(out, d + oOut, C * K * 4, hipMemcpyDeviceToHost, st), "D2H prod3"))) return rc;
+  return c->sync();
 }
 
 // out[i] = base[i]^E[mod_idx[i]] * base2[i]^exp2[i] mod N[mod_idx[i]] through the

@@ -1,7 +1,11 @@
 // Montgomery-form checks of the batched collect() job (gfx950), on the
 // lane-distributed radix-2^29 arithmetic of mont29.hpp:
 //   eq_check        a*b == c*d (mod N), optionally c < N      PDL u2/u3, RP, correct-key, DLog
+//                   (each product below R N: a factor of each pair is below N; the two
+//                   canonical residues are compared in every digit of every lane, OR-ed
+//                   over the group by mont29.hpp's group_or; parity entry fsdkr_eq_check)
 //   prod3           a*b*c mod N (exact)                        range_proofs.rs:136-148 (w, u)
+//                   (any operands below 2^(32 K32); parity entry fsdkr_prod3)
 //   inverse         launcher of the lane-cooperative Pornin inverse (inverse.hip)
 //                   mod_inv / unit tests                       zk_pdl_with_slack.rs:180, range_proofs.rs:129,142
 #include "mont29.hpp"
@@ -88,10 +92,8 @@ __global__ __launch_bounds__(BLOCK) void eq_check_kernel(const EqCheckArgs a) {
   uint32_t diff = 0;
 #pragma unroll
   for (int j = 0; j < L; ++j) diff |= x[j] ^ y[j];
-  // group-wide OR
-  if constexpr (G >= 2) diff |= __builtin_amdgcn_mov_dpp(diff, 0xB1, 0xF, 0xF, false);
-  if constexpr (G == 4) diff |= __builtin_amdgcn_mov_dpp(diff, 0x4E, 0xF, 0xF, false);
-  bool ok = (diff == 0);
+  // every lane's digits count: the verdict is lane 0's, so the OR is group-wide
+  bool ok = (group_or<G>(diff) == 0);
   if (op.flags & 1u) {
     // c < N  (c is a proof value compared for exact equality in the reference);
     // digits of c beyond KD do not exist: c < 2^(32*K32) <= R, so exactness holds

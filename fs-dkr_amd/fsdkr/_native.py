@@ -293,6 +293,13 @@ def lib():
     L.fsdkr_alice_prove.restype = ctypes.c_int
     L.fsdkr_resp_ct.argtypes = [vp, ctypes.c_uint32, u32p, u32p, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p]
     L.fsdkr_resp_ct.restype = ctypes.c_int
+    L.fsdkr_eq_check.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p, ctypes.c_uint32,
+                                 u32p, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p, u32p, u32p, u32p,
+                                 ctypes.c_uint32, u32p, u8p]
+    L.fsdkr_eq_check.restype = ctypes.c_int
+    L.fsdkr_prod3.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p, ctypes.c_uint32,
+                              u32p, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p, u32p]
+    L.fsdkr_prod3.restype = ctypes.c_int
     _lib = L
     return L
 
@@ -828,6 +835,55 @@ class Context:
         self.check(self._lib.fsdkr_pdl_u1_check(self._h, len(s1s), _ptr(S), sl, _ptr(E), _ptr(Qp), _ptr(Up),
                                                 out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
         return out
+
+    def eq_check(self, a, b, c, d, mods, mod_idx, mod_limbs, lens=None, sel=None, sel_bits=None, flags=None):
+        """[a_i b_i == c_i d'_i (mod mods[mod_idx_i]), and c_i < N where flags_i & 1] as
+        uint8 0/1 straight from eq_check_kernel (fsdkr_eq_check).  lens: limbs of the
+        a, b, c, d rows (default: mod_limbs each).  sel_i: None (always d_i) or a bit
+        index into sel_bits (a list of 32-bit words): d'_i = d_i if the bit is set,
+        else 1.  FsdkrError(FSDKR_E_ARG) for a row outside the kernel's precondition
+        (a or b, and c or d', below the modulus) or an even modulus."""
+        count = len(a)
+        if not (len(b) == len(c) == len(d) == len(mod_idx) == count):
+            raise ValueError("eq_check: argument lists differ in length")
+        out = np.zeros(count, dtype=np.uint8)
+        if count == 0:
+            return out
+        al, bl, cl, dl = lens or (mod_limbs,) * 4
+        A, B = ints_to_limbs(list(a), al), ints_to_limbs(list(b), bl)
+        Cc, D = ints_to_limbs(list(c), cl), ints_to_limbs(list(d), dl)
+        Mo = ints_to_limbs(list(mods), mod_limbs)
+        I = np.ascontiguousarray(np.asarray(mod_idx, dtype=np.uint32))
+        S = W = F = None
+        if sel is not None:
+            S = np.ascontiguousarray(np.asarray([0xFFFFFFFF if v is None else v for v in sel], dtype=np.uint32))
+            W = np.ascontiguousarray(np.asarray(list(sel_bits or [0]), dtype=np.uint32))
+        if flags is not None:
+            F = np.ascontiguousarray(np.asarray(flags, dtype=np.uint32))
+        if (S is not None and len(S) != count) or (F is not None and len(F) != count):
+            raise ValueError("eq_check: sel / flags differ in length from the rows")
+        self.check(self._lib.fsdkr_eq_check(self._h, mod_limbs, count, _ptr(A), al, _ptr(B), bl, _ptr(Cc), cl, _ptr(D), dl,
+                                            _ptr(S) if S is not None else None, _ptr(W) if W is not None else None,
+                                            _ptr(F) if F is not None else None, _ptr(Mo), len(mods), _ptr(I),
+                                            out.ctypes.data_as(u8p)))
+        return out
+
+    def prod3(self, a, b, c, mods, mod_idx, mod_limbs, lens=None):
+        """[a_i b_i c_i mod mods[mod_idx_i]] straight from prod3_kernel (fsdkr_prod3);
+        lens: limbs of the a, b, c rows (default: mod_limbs each)."""
+        count = len(a)
+        if not (len(b) == len(c) == len(mod_idx) == count):
+            raise ValueError("prod3: argument lists differ in length")
+        if count == 0:
+            return []
+        al, bl, cl = lens or (mod_limbs,) * 3
+        A, B, Cc = ints_to_limbs(list(a), al), ints_to_limbs(list(b), bl), ints_to_limbs(list(c), cl)
+        Mo = ints_to_limbs(list(mods), mod_limbs)
+        I = np.ascontiguousarray(np.asarray(mod_idx, dtype=np.uint32))
+        O = np.zeros((count, mod_limbs), dtype=np.uint32)
+        self.check(self._lib.fsdkr_prod3(self._h, mod_limbs, count, _ptr(A), al, _ptr(B), bl, _ptr(Cc), cl, _ptr(Mo),
+                                         len(mods), _ptr(I), _ptr(O)))
+        return limbs_to_ints(O)
 
     def feldman_check(self, vss, commit, n, t):
         """vss: [n_msgs][t+1] points, commit: [n_msgs*n] points -> uint8 verdicts [n_msgs*n]."""

@@ -766,6 +766,43 @@ int fsdkr_ring_pedersen_verify(fsdkr_ctx* ctx, uint32_t nl, uint32_t count, uint
                                const uint32_t* S, const uint32_t* T, const uint32_t* N, const uint32_t* A,
                                const uint32_t* Z, uint8_t* verdict);
 
+/* Parity entry of eq_check_kernel (vmont.hip), the kernel that gives the verdict
+ * of every ring-Pedersen, PDL u2 / u3, correct-key and composite-DLog check:
+ * out[i] = 1 iff a[i] b[i] == c[i] d'[i] (mod N), N = mods[mod_idx[i]], and, where
+ * flags[i] bit 0 is set, c[i] < N as an integer; else 0.  a, b, c, d: [count]
+ * rows of a_len, b_len, c_len, d_len limbs (1 .. mod_limbs; c: 1 .. 2 mod_limbs).
+ * d'[i] = d[i] if sel[i] = 0xFFFFFFFF or bit sel[i] of sel_bits (bit sel & 31 of
+ * word sel >> 5) is set, else the constant 1, which the entry supplies; sel_bits
+ * holds every word a row indexes.  sel = NULL: always d; flags = NULL: none set.
+ * mods: [n_mod][mod_limbs], odd and > 1 (else FSDKR_E_ARG); mod_limbs one of 64,
+ * 96, 128, 192 (else FSDKR_E_UNSUPPORTED).  The rows go to the device as given:
+ * the entry runs the modulus setup and the one kernel launch and nothing else.
+ *
+ * Precondition, refused with FSDKR_E_ARG where a row is outside it: the kernel
+ * reduces each side with one conditional subtraction, so each product must be
+ * below R N (R = 2^(29 KD) > 2^(32 mod_limbs)); the entry asks that a or b, and
+ * c or d', be below N.  A c with a nonzero limb above mod_limbs is accepted only
+ * with the c < N flag (verdict 0); the products never see those limbs.  Every
+ * caller in the library keeps to it for adversarial fields as well:
+ *   PDL u2       a, b, d reduced device results (d = 1 in the joint form); c = u2 raw
+ *   PDL u3       a, b, d reduced device results (b = 1 for a negative s3); c = u3 raw
+ *   ring-Pedersen  a = T^Z reduced, b = 1; c = A raw; d = S reduced on the host
+ *                modulo the odd part of N, or 1 by the challenge bit
+ *   DLog         a, b reduced device results; c = x raw, d = 1
+ *   correct key  a reduced, b = 1; c = rho reduced on the host, d = 1 */
+int fsdkr_eq_check(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const uint32_t* a, uint32_t a_len,
+                   const uint32_t* b, uint32_t b_len, const uint32_t* c, uint32_t c_len, const uint32_t* d,
+                   uint32_t d_len, const uint32_t* sel, const uint32_t* sel_bits, const uint32_t* flags,
+                   const uint32_t* mods, uint32_t n_mod, const uint32_t* mod_idx, uint8_t* out);
+/* Parity entry of prod3_kernel (vmont.hip): out[i] = a[i] b[i] c[i] mod N, exact,
+ * N = mods[mod_idx[i]]; rows of a_len, b_len, c_len limbs (1 .. mod_limbs) as given,
+ * out: [count][mod_limbs]; moduli and widths as fsdkr_eq_check.  No precondition on
+ * the operands: the two closing products by R^2 mod N bring any value below
+ * 2^(32 mod_limbs) under 2N before the one conditional subtraction. */
+int fsdkr_prod3(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const uint32_t* a, uint32_t a_len,
+                const uint32_t* b, uint32_t b_len, const uint32_t* c, uint32_t c_len, const uint32_t* mods,
+                uint32_t n_mod, const uint32_t* mod_idx, uint32_t* out);
+
 /* The prime walk above it (kzen-paillier Paillier::keypair_with_modulus_size's
  * prime generation, restated: the walk oracle/keygen.py follows).  `count`
  * probable primes of `bits` bits (bits >= 64; top two bits set) by independent
