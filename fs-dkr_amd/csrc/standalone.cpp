@@ -472,6 +472,94 @@ int fsdkr_prod3(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const uint32
   return c->sync();
 }
 
+// ---- parity entry of pow2.hip's pow2_check_kernel ---------------------------------
+// One Pow2Op per row over the rows as given and the one launch: nothing is reduced,
+// shortened or recomputed on the host.  A cleared presence bit passes address 0.
+int fsdkr_pow2_check(fsdkr_ctx* ctx, uint32_t count, const uint32_t* a, uint32_t a_len, const uint32_t* ea,
+                     uint32_t ea_len, const uint32_t* b, uint32_t b_len, const uint32_t* eb, uint32_t eb_len,
+                     const uint32_t* cc, uint32_t c_len, const uint32_t* dd, uint32_t d_len, const uint32_t* kbits,
+                     const uint32_t* sel, const uint32_t* present, const uint32_t* sel_bits, uint32_t sel_words,
+                     uint8_t* out) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return FSDKR_E_ARG;
+  const char* who = "fsdkr_pow2_check";
+  if (count == 0) return FSDKR_OK;
+  if (!a || !ea || !b || !eb || !cc || !dd || !kbits || !out || (sel_words && !sel_bits)) {
+    c->fail("%s: null pointer", who);
+    return FSDKR_E_ARG;
+  }
+  if (!a_len || !ea_len || !b_len || !eb_len || !c_len || !d_len) {
+    c->fail("%s: rows of at least one limb", who);
+    return FSDKR_E_ARG;
+  }
+  for (uint32_t i = 0; i < count; ++i) {
+    if (kbits[i] == 0 || kbits[i] > 3072) {
+      c->fail("%s: row %u: kbits %u outside 1 .. 3072", who, i, kbits[i]);
+      return FSDKR_E_ARG;
+    }
+    if (sel && sel[i] != 0xFFFFFFFFu && (sel[i] >> 5) >= sel_words) {
+      c->fail("%s: row %u: sel %u past the %u words of sel_bits", who, i, sel[i], sel_words);
+      return FSDKR_E_ARG;
+    }
+  }
+  const size_t C = count;
+  const uint32_t* src[6] = {a, ea, b, eb, cc, dd};
+  const uint32_t len[6] = {a_len, ea_len, b_len, eb_len, c_len, d_len};
+  size_t off = 0, o_row[6];
+  auto take = [&](size_t bytes) { const size_t o = off; off = al256(off + (bytes ? bytes : 1)); return o; };
+  for (int r = 0; r < 6; ++r) o_row[r] = take(C * len[r] * 4);
+  const size_t oBits = take((size_t)sel_words * 4), oOps = take(C * sizeof(Pow2Op)), oOut = take(C * 4);
+  uint8_t* d = (uint8_t*)c->buf("p2p_io", off);
+  if (!d) {
+    c->fail("%s: device allocation failed", who);
+    return FSDKR_E_OOM;
+  }
+  std::vector<Pow2Op> ops(C);
+  for (size_t i = 0; i < C; ++i) {
+    const uint32_t have = present ? present[i] : 0x3Fu;
+    uint64_t addr[6];
+    for (int r = 0; r < 6; ++r) addr[r] = ((have >> r) & 1u) ? (uint64_t)(uintptr_t)(d + o_row[r] + i * len[r] * 4) : 0;
+    Pow2Op& o = ops[i];
+    o = Pow2Op{};
+    o.a = addr[0];
+    o.ea = addr[1];
+    o.b = addr[2];
+    o.eb = addr[3];
+    o.c = addr[4];
+    o.d = addr[5];
+    o.a_len = a_len;
+    o.ea_len = ea_len;
+    o.b_len = b_len;
+    o.eb_len = eb_len;
+    o.c_len = c_len;
+    o.d_len = d_len;
+    o.sel = sel ? sel[i] : 0xFFFFFFFFu;
+    o.kbits = kbits[i];
+  }
+  hipStream_t st = c->stream;
+  int rc;
+  auto up = [&](size_t o, const void* s, size_t bytes) {
+    return c->hip_check(hipMemcpyAsync(d + o, s, bytes, hipMemcpyHostToDevice, st), "H2D pow2_check");
+  };
+  for (int r = 0; r < 6; ++r)
+    if ((rc = up(o_row[r], src[r], C * len[r] * 4))) return rc;
+  if ((sel_words && (rc = up(oBits, sel_bits, (size_t)sel_words * 4))) ||
+      (rc = up(oOps, ops.data(), C * sizeof(Pow2Op))) ||
+      (rc = c->hip_check(hipMemsetAsync(d + oOut, 0, C * 4, st), "memset pow2_check")))
+    return rc;
+  Pow2Args pa{(const Pow2Op*)(d + oOps), (const uint32_t*)(d + oBits), (uint32_t*)(d + oOut), count};
+  c->mark("pow2_check", true);
+  rc = c->hip_check(launch_pow2_check(pa, st), "pow2_check");
+  c->mark("pow2_check", false);
+  if (rc) return rc;
+  std::vector<uint32_t> res(C);
+  if ((rc = c->hip_check(hipMemcpyAsync(res.data(), d + oOut, C * 4, hipMemcpyDeviceToHost, st), "D2H pow2_check")))
+    return rc;
+  if ((rc = c->sync())) return rc;
+  for (size_t i = 0; i < C; ++i) out[i] = (uint8_t)res[i];
+  return FSDKR_OK;
+}
+
 // out[i] = base[i]^E[mod_idx[i]] * base2[i]^exp2[i] mod N[mod_idx[i]] through the
 // split chains of collect()'s GA (head over E's bits >= 256, joint tail), for
 // parity tests of that path (modexp.hip modexp_tail_kernel).

@@ -300,6 +300,9 @@ def lib():
     L.fsdkr_prod3.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p, ctypes.c_uint32,
                               u32p, ctypes.c_uint32, u32p, ctypes.c_uint32, u32p, u32p]
     L.fsdkr_prod3.restype = ctypes.c_int
+    L.fsdkr_pow2_check.argtypes = [vp, ctypes.c_uint32] + [u32p, ctypes.c_uint32] * 6 + [u32p, u32p, u32p, u32p,
+                                                                                          ctypes.c_uint32, u8p]
+    L.fsdkr_pow2_check.restype = ctypes.c_int
     _lib = L
     return L
 
@@ -884,6 +887,38 @@ class Context:
         self.check(self._lib.fsdkr_prod3(self._h, mod_limbs, count, _ptr(A), al, _ptr(B), bl, _ptr(Cc), cl, _ptr(Mo),
                                          len(mods), _ptr(I), _ptr(O)))
         return limbs_to_ints(O)
+
+    def pow2_check(self, a, ea, b, eb, c, d, kbits, lens, sel=None, sel_bits=None):
+        """[a_i^ea_i b_i^eb_i == c_i d'_i (mod 2^kbits_i)] as uint8 0/1 straight from
+        pow2_check_kernel (fsdkr_pow2_check).  a .. d: lists of ints, None for an absent
+        operand (the kernel gets address 0: the value 1, exponent 0 for ea / eb).  lens:
+        limbs of the a, ea, b, eb, c, d rows.  sel_i: None (d_i whenever present) or a
+        bit index into sel_bits (a list of 32-bit words): d'_i = d_i if the bit is set,
+        else 1.  FsdkrError(FSDKR_E_ARG) for kbits outside 1 .. 3072 or a sel past
+        sel_bits; ValueError for a value wider than its row."""
+        cols = [list(v) for v in (a, ea, b, eb, c, d)]
+        count = len(cols[0])
+        if not all(len(v) == count for v in cols) or len(kbits) != count or (sel is not None and len(sel) != count):
+            raise ValueError("pow2_check: argument lists differ in length")
+        out = np.zeros(count, dtype=np.uint8)
+        if count == 0:
+            return out
+        rows = [ints_to_limbs([0 if x is None else x for x in v], l) for v, l in zip(cols, lens)]
+        present = np.asarray([sum((v[i] is not None) << r for r, v in enumerate(cols)) for i in range(count)],
+                             dtype=np.uint32)
+        Kb = np.ascontiguousarray(np.asarray(kbits, dtype=np.uint32))
+        S = W = None
+        if sel is not None:
+            S = np.ascontiguousarray(np.asarray([0xFFFFFFFF if v is None else v for v in sel], dtype=np.uint32))
+        if sel_bits:
+            W = np.ascontiguousarray(np.asarray(list(sel_bits), dtype=np.uint32))
+        args = [self._h, count]
+        for r, l in zip(rows, lens):
+            args += [_ptr(r), l]
+        self.check(self._lib.fsdkr_pow2_check(*args, _ptr(Kb), _ptr(S) if S is not None else None, _ptr(present),
+                                              _ptr(W) if W is not None else None, 0 if W is None else len(W),
+                                              out.ctypes.data_as(u8p)))
+        return out
 
     def feldman_check(self, vss, commit, n, t):
         """vss: [n_msgs][t+1] points, commit: [n_msgs*n] points -> uint8 verdicts [n_msgs*n]."""

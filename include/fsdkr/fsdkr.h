@@ -802,6 +802,26 @@ int fsdkr_eq_check(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const uin
 int fsdkr_prod3(fsdkr_ctx* ctx, uint32_t mod_limbs, uint32_t count, const uint32_t* a, uint32_t a_len,
                 const uint32_t* b, uint32_t b_len, const uint32_t* c, uint32_t c_len, const uint32_t* mods,
                 uint32_t n_mod, const uint32_t* mod_idx, uint32_t* out);
+/* Parity entry of pow2_check_kernel (pow2.hip), the 2-adic half of every ring-
+ * Pedersen and composite-DLog check whose modulus is even (N = 2^k m, m odd):
+ * out[i] = 1 iff a[i]^ea[i] b[i]^eb[i] == c[i] d'[i] (mod 2^kbits[i]), else 0.
+ * a, ea, b, eb, c, d: [count] rows of a_len .. d_len limbs, each >= 1; a row
+ * shorter than ceil(kbits / 32) limbs is zero-extended, a longer one is cut at
+ * 2^kbits (exponent rows are read whole).  present[i]: bit 0 a, 1 ea, 2 b, 3 eb,
+ * 4 c, 5 d; a cleared bit hands the kernel address 0 for that operand, which it
+ * reads as the value 1 (exponent 0 for ea, eb; the row's limbs are then ignored);
+ * present = NULL: all six.  d'[i] = d[i] if d is present and sel[i] = 0xFFFFFFFF or
+ * bit sel[i] of sel_bits (bit sel & 31 of word sel >> 5) is set, else 1; sel =
+ * NULL: always d.  sel_bits: sel_words words (NULL with 0 words).  Refused with
+ * FSDKR_E_ARG: kbits[i] = 0 or > 3072 (the kernel answers 0 there; no caller emits
+ * them), a sel[i] at or past bit 32 sel_words, a row width of 0, a null pointer
+ * other than sel, present and an empty sel_bits.  The rows go to the device as
+ * given: the entry builds one descriptor per row and runs the one kernel launch. */
+int fsdkr_pow2_check(fsdkr_ctx* ctx, uint32_t count, const uint32_t* a, uint32_t a_len, const uint32_t* ea,
+                     uint32_t ea_len, const uint32_t* b, uint32_t b_len, const uint32_t* eb, uint32_t eb_len,
+                     const uint32_t* c, uint32_t c_len, const uint32_t* d, uint32_t d_len, const uint32_t* kbits,
+                     const uint32_t* sel, const uint32_t* present, const uint32_t* sel_bits, uint32_t sel_words,
+                     uint8_t* out);
 
 /* The prime walk above it (kzen-paillier Paillier::keypair_with_modulus_size's
  * prime generation, restated: the walk oracle/keygen.py follows).  `count`

@@ -196,10 +196,12 @@ def test_oversize_ek_moduli_too_small(gpu_ctx):
 
 
 # --------------------------------------------------------------- even moduli --
-def _even_rp(st, rp_pf, twos, rng):
+def _even_rp(st, rp_pf, twos, rng, reduce=True):
     """A VALID ring-Pedersen proof for N' = 2^twos * N: T' odd with T' = T (mod N),
     S' = T'^lam, A_i = T'^a_i mod N', Z_i = a_i + e_i lam mod phi(N) (T'^phi = 1
-    mod 2^twos for twos <= 4, since 4 | phi)."""
+    mod 2^twos for twos <= 4, since 4 | phi); reduce=False leaves Z_i = a_i + e_i lam
+    as an integer, which holds modulo any N'."""
+    assert twos <= 4 or not reduce
     N2 = st.N << twos
     T2 = st.T if st.T & 1 else st.T + st.N
     lam = rng.sample_below(st.phi)
@@ -211,8 +213,26 @@ def _even_rp(st, rp_pf, twos, rng):
         if 8 * len(eb) >= M:
             break
     bits = [(eb[i >> 3] >> (i & 7)) & 1 for i in range(M)]
-    Z = [(a[i] + bits[i] * lam) % st.phi for i in range(M)]
+    Z = [(a[i] + bits[i] * lam) % st.phi if reduce else a[i] + bits[i] * lam for i in range(M)]
     return RingPedersenStatement(S2, T2, N2, st.phi, st.ek), RingPedersenProof(tuple(A), tuple(Z))
+
+
+def _pow2_rp(st, k, rng):
+    """A VALID ring-Pedersen proof for N = 2^k alone (odd part 1: the 2-adic half decides
+    every check): T odd, S = T^lam, A_i = T^a_i, Z_i = a_i + e_i lam as integers."""
+    N = 1 << k
+    T = rng.sample_below(N) | 1
+    lam = rng.sample_below(1 << 200)
+    S = pow(T, lam, N)
+    while True:
+        a = [rng.sample_below(1 << 200) for _ in range(M)]
+        A = [pow(T, x, N) for x in a]
+        eb = bigint.to_bytes(chain_bigint(*A))
+        if 8 * len(eb) >= M:
+            break
+    bits = [(eb[i >> 3] >> (i & 7)) & 1 for i in range(M)]
+    Z = [a[i] + bits[i] * lam for i in range(M)]
+    return RingPedersenStatement(S, T, N, st.phi, st.ek), RingPedersenProof(tuple(A), tuple(Z))
 
 
 def test_even_ring_pedersen_modulus(gpu_ctx, dkr5):
@@ -230,6 +250,21 @@ def test_even_ring_pedersen_modulus(gpu_ctx, dkr5):
         m4[1].ring_pedersen_proof = RingPedersenProof(
             tuple(x + (st.N >> twos) if k == 3 else x for k, x in enumerate(pf.A)), pf.Z)
         _check(gpu_ctx, m4, keys[0], dks[0])
+    # twos = 40 (two limbs of 2^k; Z unreduced) and N = 2^1000 alone: the valid proof, and
+    # A_3 changed modulo 2^k only (+ odd part * 2^(k-1)), which the 2-adic half alone can reject
+    for which in ("twos40", "pure"):
+        m2 = copy.deepcopy(msgs)
+        st0 = m2[1].ring_pedersen_statement
+        st, pf = _even_rp(st0, None, 40, rng, reduce=False) if which == "twos40" else _pow2_rp(st0, 1000, rng)
+        k = (st.N & -st.N).bit_length() - 1
+        assert k == (40 if which == "twos40" else 1000) and (st.N >> k == 1) == (which == "pure")
+        m2[1].ring_pedersen_statement, m2[1].ring_pedersen_proof = st, pf
+        ro = _check(gpu_ctx, m2, keys[0], dks[0])
+        assert ro is None, ro
+        m4 = copy.deepcopy(m2)
+        m4[1].ring_pedersen_proof = RingPedersenProof(
+            tuple((x + (st.N >> 1)) % st.N if i == 3 else x for i, x in enumerate(pf.A)), pf.Z)
+        _check(gpu_ctx, m4, keys[0], dks[0], expect="RingPedersenProofError")
     # N = 0: the first mod_pow divides by zero
     m5 = copy.deepcopy(msgs)
     s = m5[4].ring_pedersen_statement
@@ -288,6 +323,47 @@ def test_even_dlog_modulus(gpu_ctx):
     p = j3.composite_dlog_proof_base_h2
     j3.composite_dlog_proof_base_h2 = CompositeDLogProof((p.x + Nt) % N2, p.y)
     _check(gpu_ctx, msgs, keys[1], dks[1], [j3], expect="DLogProofValidation")
+    # N' = 2^40 N~ (two limbs of 2^k): Phi = 2^40 phi is a multiple of the group's exponent, and a
+    # secret coprime to phi is odd, hence invertible modulo Phi
+    twos = 40
+    N2 = Nt << twos
+    Phi = phi << twos
+    xinv = pow(xhi, -1, Phi)
+    ni = pow(g, xhi, N2)
+    assert pow(ni, xinv, N2) == g
+    s1, s2 = DLogStatement(N2, g, ni), DLogStatement(N2, ni, g)
+    j4 = copy.deepcopy(jm)
+    j4.dlog_statement = s1
+    j4.composite_dlog_proof_base_h1 = prove(s1, Phi - xhi)
+    j4.composite_dlog_proof_base_h2 = prove(s2, Phi - xinv)
+    assert j4.composite_dlog_proof_base_h1.verify(s1) and j4.composite_dlog_proof_base_h2.verify(s2)
+    ro = _check(gpu_ctx, msgs, keys[1], dks[1], [j4])
+    assert ro is None, ro
+    j5 = copy.deepcopy(j4)
+    p = j5.composite_dlog_proof_base_h2
+    j5.composite_dlog_proof_base_h2 = CompositeDLogProof((p.x + Nt) % N2, p.y)
+    _check(gpu_ctx, msgs, keys[1], dks[1], [j5], expect="DLogProofValidation")
+    # N = 2^200 alone (odd part 1: the 2-adic half decides): g odd, ni = g^-s, g = ni^-s'
+    # with s s' = 1 modulo 2^198, the exponent of the group
+    N2 = 1 << 200
+    g = rng.sample_below(N2) | 1
+    s = rng.sample_below(1 << 198) | 1
+    s_inv = pow(s, -1, 1 << 198)
+    ni = pow(g, (1 << 198) - s, N2)
+    assert pow(ni, (1 << 198) - s_inv, N2) == g
+    s1, s2 = DLogStatement(N2, g, ni), DLogStatement(N2, ni, g)
+    j6 = copy.deepcopy(jm)
+    j6.dlog_statement = s1
+    j6.composite_dlog_proof_base_h1 = prove(s1, s)
+    j6.composite_dlog_proof_base_h2 = prove(s2, s_inv)
+    assert j6.composite_dlog_proof_base_h1.verify(s1) and j6.composite_dlog_proof_base_h2.verify(s2)
+    ro_valid = _check(gpu_ctx, msgs, keys[1], dks[1], [j6])
+    j7 = copy.deepcopy(j6)
+    p = j7.composite_dlog_proof_base_h1
+    j7.composite_dlog_proof_base_h1 = CompositeDLogProof((p.x + (1 << 199)) % N2, p.y)
+    assert not j7.composite_dlog_proof_base_h1.verify(s1)
+    ro_bad = _check(gpu_ctx, msgs, keys[1], dks[1], [j7], expect="DLogProofValidation")
+    assert ro_valid != ro_bad
 
 
 # ------------------------------------------------ share recovery in the order --
